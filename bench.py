@@ -11,6 +11,10 @@ steps as in training; if the timed window contains none, one outer step (pseudo-
 RCCL all-reduce + outer Nesterov) is executed INSIDE the window anyway -- a conservative charge
 (H=100 amortises it 100x in real training).
 
+A plain run sets up, warms up, times the K steps and prints one JSON line.  ``--full`` adds the diagnostics
+that need GPU work of their own (one more outer step, serialized, for ``outer_phase_ms``).  ``--dump-outputs
+DIR`` writes what the timed steps computed (seeded inputs: identical from run to run) as ``DIR/<name>.npy``.
+
     python bench.py                       # 1 GPU, defaults
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 3
 """
@@ -112,7 +116,38 @@ def parse():
     ap.add_argument("--fp8-fused-quant", type=int, default=1, choices=[0, 1],
                     help="with --fp8: operand quantisation fused into the producing kernels (0: separate casts)")
     ap.add_argument("--profile-steps", type=int, default=0, help="extra steps under torch.profiler (not timed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the diagnostics that take GPU work of their own after the timed window (the "
+                         "serialized outer step behind outer_phase_ms); a plain run only sets up, warms up, times "
+                         "the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed as DIR/<name>.npy (float32): the last "
+                         "inner step's loss and gradient norm, and fixed seeded samples of the master weights and "
+                         "the AdamW first moment as the timed window left them (rank 0)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024  # elements per sampled flat buffer (16 MiB as float32)
+
+
+def dump_outputs(path, tr, loss):
+    """Results of the timed window as ``<name>.npy``.  Flat buffers longer than DUMP_SAMPLE are sampled at
+    sorted positions drawn from a fixed seed, so two builds given the same arguments write the same elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    opt = tr.diloco.inner_optimizer
+    n = tr.model.store.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(1337).integers(0, n, size=DUMP_SAMPLE))
+        idx = torch.from_numpy(pos).to(tr.env.device)
+    arrays = {"loss": loss.detach().reshape(1), "grad_norm": opt.last_grad_norm.reshape(1),
+              "master_weights": tr.model.store.master, "adam_exp_avg": opt.exp_avg}
+    for name, t in arrays.items():
+        if idx is not None and t.numel() == n:
+            t = t.index_select(0, idx)
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def _mlp_form():
@@ -208,9 +243,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     outer_ms = dl.comm_ms()  # device time of the last outer step (HIP events; after the timed window)
-    # one more outer step, untimed and serialized, split into pseudo-gradient / all-reduce / update
+    if a.dump_outputs and env.rank == 0 and loss is not None:
+        dump_outputs(a.dump_outputs, tr, loss)
+    # --full: one more outer step, untimed and serialized, split into pseudo-gradient / all-reduce / update
     phases = {}
-    if not a.overlap_outer and env.device.type == "cuda":
+    if a.full and not a.overlap_outer and env.device.type == "cuda":
         dl.outer_step(phases=True)
         phases = dl.outer_phase_ms()
     vals = [outer_ms] + [phases.get(k, 0.0) for k in ("pseudograd_ms", "allreduce_ms", "outer_update_ms")]
@@ -265,7 +302,7 @@ def main():
             # outer-step cost as seen by the compute stream (HIP events: pseudo-gradient + bucketed
             # RCCL all-reduce + fused Nesterov), host wall time per outer step, and calls per outer step
             "outer_step_ms": round(outer_ms, 3),
-            # the same step serialized, per phase (untimed, after the window): what RCCL costs per N
+            # --full: the same step serialized, per phase (untimed, after the window): what RCCL costs per N
             "outer_phase_ms": {k: round(v, 3) for k, v in
                                zip(("pseudograd", "allreduce", "outer_update"), vals[1:])} if phases else None,
             "outer_step_wall_ms": round(1000.0 * dl.avg_sync_time, 3),

@@ -160,7 +160,7 @@ class Diloco:
 
     # ------------------------------------------------------------------ outer step
     def outer_step(self, phases: bool = False):
-        """One outer step.  ``phases=True`` (diagnostics, e.g. bench.py after its timed window) runs it
+        """One outer step.  ``phases=True`` (diagnostics, e.g. bench.py --full after its timed window) runs it
         serialized -- every bucket's all-reduce completes before the first Nesterov update -- and
         records HIP events between the phases, so :meth:`outer_phase_ms` can split the step into
         pseudo-gradient / collective / outer-update time; the default pipelines buckets instead."""

@@ -221,6 +221,31 @@ def test_bench_contract_single_process():
 
 
 @pytest.mark.slow
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR``: float32 ``.npy`` files of what the timed steps computed, the same from run to
+    run (seeded weights and tokens); ``outer_phase_ms`` is a ``--full`` diagnostic (GPU only) and null here."""
+    import numpy as np
+    env = child_env(OMP_NUM_THREADS="2")
+    runs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable] + BENCH + ["--gpus", "1", "--dump-outputs", str(tmp_path / d)], cwd=ROOT,
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _bench_json(r.stdout)
+        assert j["steps"] == 3 and j["outer_phase_ms"] is None
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["adam_exp_avg.npy", "grad_norm.npy", "loss.npy", "master_weights.npy"]
+        arrs = {f: np.load(tmp_path / d / f) for f in files}
+        assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in arrs.values())
+        assert sum(x.nbytes for x in arrs.values()) <= 64 << 20
+        assert abs(float(arrs["loss.npy"][0]) - j["final_loss"]) < 1e-3
+        assert arrs["master_weights.npy"].shape == arrs["adam_exp_avg.npy"].shape and arrs["adam_exp_avg.npy"].any()
+        runs.append(arrs)
+    for f in runs[0]:
+        np.testing.assert_allclose(runs[0][f], runs[1][f], rtol=1e-5, atol=1e-7)
+
+
+@pytest.mark.slow
 def test_bench_contract_two_ranks_gloo():
     env = child_env(OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",

@@ -33,7 +33,7 @@ def test_bench_torchrun_one_rank_nccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "1", "--backend", "nccl",
            "--model", "llama_tiny.json", "--batch-size", "16", "--micro-batch", "8", "--seq-len", "256",
-           "--steps", "4", "--warmup", "1", "--inner-steps", "2"]
+           "--steps", "4", "--warmup", "1", "--inner-steps", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -53,7 +53,7 @@ def test_bench_default_one_gpu_runs_rccl_path():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     cmd = [sys.executable, "bench.py", "--model", "llama_tiny.json", "--batch-size", "16", "--micro-batch", "8",
-           "--seq-len", "256", "--steps", "2", "--warmup", "1", "--inner-steps", "100"]
+           "--seq-len", "256", "--steps", "2", "--warmup", "1", "--inner-steps", "100", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
