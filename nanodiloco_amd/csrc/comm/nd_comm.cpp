@@ -13,7 +13,8 @@
 //   * a consumer stream waits for one collective with nd_comm_wait(ticket) (a GPU-side event wait):
 //     bucket i's consumer kernel then overlaps the reduction of bucket i + 1;
 //   * all collectives are in place (all-gather: send = recv + rank * count), so no temporary buffer
-//     is shared between the caching allocator's stream and the communicator stream.
+//     is shared between the caching allocator's stream and the communicator stream; the one exception,
+//     the all-to-all of the quantised outer step, runs between two buffers its caller keeps for good.
 //
 // Failure detection (a dead peer must surface as an error on every rank, never a hang):
 //   * the communicator is NON-BLOCKING (ncclConfig_t.blocking = 0): ncclCommInitRankConfig and every
@@ -376,6 +377,34 @@ ND_API int nd_comm_all_gather(void* handle, void* recv, size_t count, int dtype,
   const char* send = static_cast<const char*>(recv) + (size_t)c->rank * count * dtype_bytes(dtype);
   return issue(c, producer, (int64_t)(count * dtype_bytes(dtype)), ticket, [&](ncclComm_t n) {
     return ncclAllGather(send, recv, count, (ncclDataType_t)dtype, n, c->stream);
+  });
+}
+
+// out of place: rank r's piece p (send[p * count, (p + 1) * count)) lands in rank p's recv[r * count, ...).
+// One group of ncclSend / ncclRecv to and from every rank, self included.  Inside a group of a non-blocking
+// communicator the calls may answer ncclInProgress, which is no error; ncclGroupEnd's result goes to issue(),
+// which polls it like any collective's.  The group is always closed, also after a failed call.
+ND_API int nd_comm_all_to_all(void* handle, const void* send, void* recv, size_t count_per_peer, int dtype,
+                              hipStream_t producer, int64_t* ticket) {
+  auto* c = static_cast<Comm*>(handle);
+  if (!c || !ticket || dtype_bytes(dtype) == 0 || !send || !recv || send == recv) return ND_E_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  const size_t piece = count_per_peer * dtype_bytes(dtype);
+  return issue(c, producer, (int64_t)(piece * (size_t)c->nranks), ticket, [&](ncclComm_t n) {
+    ncclResult_t bad = ncclSuccess;
+    auto keep = [&](ncclResult_t r) {
+      if (r != ncclSuccess && r != ncclInProgress && bad == ncclSuccess) bad = r;
+    };
+    keep(ncclGroupStart());
+    if (bad != ncclSuccess) return bad;
+    for (int p = 0; p < c->nranks && bad == ncclSuccess; ++p) {
+      keep(ncclSend(static_cast<const char*>(send) + (size_t)p * piece, count_per_peer, (ncclDataType_t)dtype, p, n,
+                    c->stream));
+      keep(ncclRecv(static_cast<char*>(recv) + (size_t)p * piece, count_per_peer, (ncclDataType_t)dtype, p, n,
+                    c->stream));
+    }
+    const ncclResult_t end = ncclGroupEnd();
+    return bad != ncclSuccess ? bad : end;
   });
 }
 

@@ -5,6 +5,7 @@
 // Guideline 11).  The clip coefficient never touches the host: nd_adamw_step re-reduces the
 // <=1024 per-block sum-of-squares partials in every block (4 KB, L2-resident) before its stream.
 #include "common.h"
+#include "outer_update.h"
 
 using namespace nd;
 
@@ -139,12 +140,11 @@ __global__ void __launch_bounds__(256) outer_kernel(float* __restrict__ p, float
                                                     int first, const float* __restrict__ drift) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float d = (DDT == BF16 ? bf2f(reinterpret_cast<const bf16_t*>(dsum)[i]) : reinterpret_cast<const float*>(dsum)[i]) * inv_w;
-    const float b = first ? d : mu * buf[i] + d;
+    float b = first ? 0.f : buf[i];
+    float so = sync[i];
+    const float np = outer_update(d, b, so, drift ? p[i] : 0.f, drift != nullptr, drift ? drift[i] : 0.f, lr, mu, first);
     buf[i] = b;
-    const float so = sync[i];
-    const float th = so - lr * (d + mu * b);
-    const float np = drift ? th + (p[i] - (so - drift[i])) : th;
-    sync[i] = th;
+    sync[i] = so;
     p[i] = np;
     if (SDT == BF16) reinterpret_cast<bf16_t*>(sh)[i] = f2bf(np);
   }

@@ -11,6 +11,7 @@ from .swiglu import swiglu
 from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding
 from .cross_entropy import lm_head_ce, IGNORE_INDEX
 from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov
+from .qcomm import pseudograd_q, qreduce, outer_nesterov_q
 from .determinism import set_deterministic, deterministic
 from . import reference
 
@@ -18,4 +19,5 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "set_wgrad_overlap", "wgrad_overlap_enabled", "join_wgrad", "set_wgrad_group", "wgrad_group_enabled",
            "set_dgrad_transposed", "dgrad_transposed_enabled", "transpose_into",
            "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "lm_head_ce",
-           "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "reference"]
+           "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
+           "outer_nesterov_q", "reference"]

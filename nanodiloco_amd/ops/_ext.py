@@ -165,6 +165,10 @@ def _declare(L: ctypes.CDLL):
         "nd_pseudograd": [P, P, P, I, L64, P],
         "nd_outer_nesterov": [P, P, P, I, P, P, I, L64, F, F, F, I, P, P, P],
         "nd_axpby": [P, P, L64, F, F, P],
+        # block-quantised outer transport (csrc/qcomm.hip)
+        "nd_pseudograd_q": [P, P, L64, P, L64, L64, I, P],
+        "nd_qreduce": [P, I, L64, I, P, P],
+        "nd_outer_nesterov_q": [P, P, P, I, L64, P, P, I, L64, F, F, F, I, P],
         # fp8 quantisation
         "nd_fp8_cast": [P, I, L64, P, P, I, P, I, P],
         "nd_fp8_cast_t": [P, I, I, I, L64, P, P, P, I, P, I, P],

@@ -65,6 +65,27 @@ class _RcclWork:
         return self.comm.query(self.ticket)
 
 
+class _C10dWork:
+    """A c10d work handle plus the tensors that must stay alive until it is waited for."""
+
+    __slots__ = ("work", "keep")
+
+    def __init__(self, work, keep=()):
+        self.work, self.keep = work, keep
+
+    def wait(self):
+        self.work.wait()
+        self.keep = ()
+        return True
+
+
+class _DoneWork:
+    """Handle of a collective that needed no communication (a group of one without a process group)."""
+
+    def wait(self):
+        return True
+
+
 class PendingAllReduce:
     def __init__(self, works, ranges, flat):
         self.works = works
@@ -88,7 +109,8 @@ class PendingAllReduce:
 
 
 class FlatCommunicator:
-    """Bucketed async all-reduce / broadcast / all-gather on flat buffers for one process group."""
+    """Bucketed async all-reduce / broadcast / all-gather (and the all-to-all + all-gather of quantised wire
+    buffers) on flat buffers for one process group."""
 
     def __init__(self, group, group_size: int, bucket_mb: float = 128.0, enabled: bool = True, force: bool = False,
                  impl: str = "c10d", device: Optional[torch.device] = None, timeout_s: float = 1800.0):
@@ -140,6 +162,45 @@ class FlatCommunicator:
             if on_bucket is not None:
                 on_bucket(a, b)
         return p
+
+    def all_to_all_async(self, send: torch.Tensor, recv: torch.Tensor):
+        """Out-of-place all-to-all of equal pieces: piece p of ``send`` (``size`` pieces) goes to member p,
+        the piece from member r lands at piece r of ``recv``.  Returns a handle whose ``wait()`` orders the
+        current stream (the host, on gloo) after the exchange.  Both buffers must stay alive and untouched
+        until then: the quantised outer step keeps them for the life of the run."""
+        if send.numel() % max(1, self.size) or recv.numel() != send.numel():
+            raise ValueError("all_to_all: send / recv must match and divide by the group size")
+        if not self.enabled:
+            recv.copy_(send)
+            return _DoneWork()
+        t0 = time.perf_counter()
+        if self.rccl is not None:
+            w = _RcclWork(self.rccl, self.rccl.all_to_all(send, recv))
+        else:
+            w = _C10dWork(dist.all_to_all_single(recv, send, group=self.group, async_op=True))
+        self.stats.calls += 1
+        self.stats.bytes += send.numel() * send.element_size()
+        self.stats.host_time_s += time.perf_counter() - t0
+        return w
+
+    def all_gather_async(self, out: torch.Tensor, my_index: int):
+        """All-gather of a wire buffer: member r contributed piece r of ``out`` (``size`` equal pieces; this
+        member's piece ``my_index`` is already in place).  Returns a ``wait()``-able handle."""
+        if out.numel() % max(1, self.size):
+            raise ValueError("all_gather: numel not divisible by the group size")
+        if not self.enabled:
+            return _DoneWork()
+        t0 = time.perf_counter()
+        n = out.numel() // self.size
+        if self.rccl is not None:  # in place
+            w = _RcclWork(self.rccl, self.rccl.all_gather(out))
+        else:
+            mine = out[my_index * n:(my_index + 1) * n].clone()
+            w = _C10dWork(dist.all_gather_into_tensor(out, mine, group=self.group, async_op=True), (mine,))
+        self.stats.calls += 1
+        self.stats.bytes += n * out.element_size()
+        self.stats.host_time_s += time.perf_counter() - t0
+        return w
 
     def broadcast(self, flat: torch.Tensor, src_group_rank: int = 0):
         if not self.enabled:

@@ -17,6 +17,11 @@ pseudo-gradient.  Capability parity with ``class Diloco`` (REF/nanodiloco/diloco
 
 Extensions (north star):
 * ``comm_dtype=bf16``: pseudo-gradients travel in bf16 (half the bytes / outer step);
+* ``comm_dtype="int8"`` / ``"int4"`` (``torch.int8`` = ``"int8"``): block-quantised transport, a quarter /
+  an eighth of the fp32 bytes.  Integers with per-block scales cannot be all-reduced, so the step becomes
+  ``nd_pseudograd_q`` -> all-to-all -> ``nd_qreduce`` -> all-gather -> ``nd_outer_nesterov_q`` per bucket
+  (a quantised reduce-scatter + all-gather, docs/DESIGN.md §4).  Stateless: no error feedback, nothing new
+  in a checkpoint.  Not with ``overlap=True`` yet;
 * ``overlap=True``: the all-reduce is launched at the boundary and overlaps the next inner step;
   it is applied one step late as theta <- theta_outer + (theta_local_now - theta_local_boundary)
   (streaming / delayed outer update).  ``overlap=False`` is bit-faithful to the reference order;
@@ -37,6 +42,26 @@ from ..optim import FlatAdamW, FlatOuterNesterov
 from ..utils.schedule import CosineWarmupSchedule
 from .comm import FlatCommunicator, PendingAllReduce, plan_buckets
 from .dist import DistEnv
+from ..ops import qcomm
+
+
+def quantised_bits(comm_dtype) -> int:
+    """8 / 4 for the block-quantised transports (``"int8"`` or ``torch.int8``, ``"int4"``), 0 for a plain
+    torch dtype (fp32 / bf16 all-reduce)."""
+    if isinstance(comm_dtype, str):
+        if comm_dtype in ("int8", "int4"):
+            return int(comm_dtype[3:])
+        raise ValueError(f"comm_dtype must be a torch dtype, 'int8' or 'int4', not {comm_dtype!r}")
+    return 8 if comm_dtype == torch.int8 else 0
+
+
+class _QBucket:
+    """One bucket of the quantised outer step: elements [x, y) of the owned span, W chunks of c elements."""
+
+    __slots__ = ("x", "y", "c", "send", "recv", "gath")
+
+    def __init__(self, x, y, c, send, recv, gath):
+        self.x, self.y, self.c, self.send, self.recv, self.gath = x, y, c, send, recv, gath
 
 
 class Diloco:
@@ -63,6 +88,10 @@ class Diloco:
         self.outer_steps = outer_steps if outer_steps is not None else max(1, total_steps // max(1, inner_steps))
         self.env = env or DistEnv(device=self.store.device)
         self.scheduler = CosineWarmupSchedule(inner_optimizer.lr, warmup_steps, total_steps)
+        self.qbits = quantised_bits(comm_dtype)  # 0: fp32 / bf16 transport
+        if self.qbits and overlap:
+            raise ValueError("quantised transport (comm_dtype int8 / int4) does not support overlap=True yet: the "
+                             "delayed application and its pending-state checkpoint need the fp32 / bf16 path")
         self.comm_dtype = comm_dtype
         self.overlap = overlap
         self.offload_snapshot = offload_snapshot
@@ -92,7 +121,12 @@ class Diloco:
         else:
             self.sync = self.store.master.clone()
         a, b = self.my_shard
-        self.delta = torch.zeros(b - a, dtype=comm_dtype, device=self.store.device)
+        if self.qbits:
+            # the fp32 pseudo-gradient is never materialised: it is quantised in registers into the wire buffers
+            self.delta = torch.zeros(0, dtype=torch.float32, device=self.store.device)
+            self._qplan = self._plan_quantised(b - a)
+        else:
+            self.delta = torch.zeros(b - a, dtype=comm_dtype, device=self.store.device)
         self.drift_base = torch.zeros(b - a, dtype=torch.float32, device=self.store.device) if overlap else None
         self._pending = None
         self._sync_time = 0.0
@@ -119,6 +153,8 @@ class Diloco:
     @property
     def bytes_per_outer_step(self) -> int:
         """Pseudo-gradient payload each GPU contributes to the outer all-reduce."""
+        if self.qbits:  # phase-1 (all-to-all) wire bytes: codes + scales of every chunk, padding included
+            return sum(bk.send.numel() for bk in self._qplan) if self.outer_comm.enabled else 0
         a, b = self.my_shard
         return (b - a) * torch.tensor([], dtype=self.comm_dtype).element_size() if self.outer_comm.enabled else 0
 
@@ -137,6 +173,8 @@ class Diloco:
         """Number of all-reduce calls one outer step issues (the reference issues one per tensor)."""
         if not self.outer_comm.enabled:
             return 0
+        if self.qbits:  # each bucket issues two collectives: an all-to-all and an all-gather
+            return len(self._qplan)
         a, b = self.my_shard
         return len(plan_buckets(0, b - a, self.delta.element_size(), self.outer_comm.bucket_bytes))
 
@@ -172,6 +210,8 @@ class Diloco:
         master = self.store.master
         sync = self._sync_on_device()
         a, b = self.my_shard
+        if self.qbits:
+            return self._outer_step_quantised(sync, ev0, t0, phases and cuda)
         ops.pseudograd(sync[a:b], master[a:b], self.delta)
         if self.overlap:
             # fp32 drift base: with bf16 transport, re-applying the local progress from the rounded
@@ -226,6 +266,11 @@ class Diloco:
             ops.outer_nesterov(master[ga:gb], sync[ga:gb], self.delta[x:y], mom[ga:gb],
                                sh_full[ga:gb] if sh_full is not None else None, inv_w, opt.lr, opt.momentum,
                                first, drift_base=self.drift_base[x:y] if self.overlap else None)
+        self._after_update(sync, sh_full, ev0, t1 if self.overlap else t0)
+
+    def _after_update(self, sync, sh_full, ev0, t_from):
+        """What follows the per-bucket updates of an outer step, whatever the transport."""
+        opt, master = self.outer_optimizer, self.store.master
         opt.step_count += 1
         self.store.version += 1
         # own RCCL: a watchdog abort still completes the collective's event, so the update above may have
@@ -245,10 +290,74 @@ class Diloco:
             ev1 = torch.cuda.Event(enable_timing=True)
             ev1.record()
             self._comm_events = [(ev0, ev1)]
-        self._sync_time += time.perf_counter() - (t1 if self.overlap else t0)
+        self._sync_time += time.perf_counter() - t_from
         self._sync_calls += 1
         if self.debug_checks:
             self.check_replicas()
+
+    # ------------------------------------------------------------------ quantised transport
+    def _plan_quantised(self, length: int) -> list:
+        """Buckets of the span this GPU owns, in elements: each a multiple of W*256 (W chunks of whole
+        quantisation blocks) except the last, which is padded in its wire buffers.  Per bucket three
+        persistent uint8 wire buffers of W chunks: ``send`` (this worker's quantised delta, chunk w for worker
+        w), ``recv`` (chunk ``worker`` of every worker) and ``gath`` (the reduced chunks of all workers)."""
+        w = max(1, self.env.num_workers)
+        bits, unit = self.qbits, w * qcomm.QBLOCK
+        per = max(unit, (self.outer_comm.bucket_bytes * 8 // bits) // unit * unit)
+        dev = self.store.device
+        plan = []
+        for x, y in plan_buckets(0, length, 1, per, align=unit):
+            c = qcomm.chunk_elems(y - x, w)
+            nbytes = w * qcomm.chunk_bytes(c, bits)
+            plan.append(_QBucket(x, y, c, *(torch.zeros(nbytes, dtype=torch.uint8, device=dev) for _ in range(3))))
+        return plan
+
+    def _outer_step_quantised(self, sync, ev0, t0, phases: bool):
+        """int8 / int4 transport: per bucket quantise -> all-to-all -> dequantise, sum, requantise ->
+        all-gather -> update.  Every bucket's quantise + all-to-all is issued first, then each bucket is
+        reduced and its all-gather issued, then each bucket is updated while the next one is still being
+        gathered; the host never blocks (GPU).  EVERY worker, the owner of a chunk included, updates from
+        the gathered bytes, so theta_sync and the master stay bit-identical across workers."""
+        e, opt, bits = self.env, self.outer_optimizer, self.qbits
+        w, r = max(1, e.num_workers), e.worker
+        a, _ = self.my_shard
+        master, shadow, mom = self.store.master, self.store.shadow, opt.momentum_buffer
+        sh_full = shadow if shadow.data_ptr() != master.data_ptr() else None
+        first = opt.step_count == 0
+        inv_w = 1.0 / w
+        comm = self.outer_comm
+
+        def mark():
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            return ev
+
+        exchanged = []
+        for bk in self._qplan:
+            ga, gb = a + bk.x, a + bk.y
+            ops.pseudograd_q(sync[ga:gb], master[ga:gb], bk.send, w, bk.c, bits)
+            exchanged.append(comm.all_to_all_async(bk.send, bk.recv))
+        marks = [ev0, mark()] if phases else None
+        gathered = []
+        for bk, work in zip(self._qplan, exchanged):
+            work.wait()
+            pb = bk.send.numel() // w
+            ops.qreduce(bk.recv, w, bk.c, bits, bk.gath[r * pb:(r + 1) * pb])
+            gathered.append(comm.all_gather_async(bk.gath, r))
+        if phases:
+            for work in gathered:
+                work.wait()  # serialized: the compute stream waits for every bucket here
+            marks.append(mark())
+        self.outer_step_count += 1
+        for bk, work in zip(self._qplan, gathered):
+            work.wait()
+            ga, gb = a + bk.x, a + bk.y
+            ops.outer_nesterov_q(master[ga:gb], sync[ga:gb], bk.gath, w, bk.c, bits, mom[ga:gb],
+                                 sh_full[ga:gb] if sh_full is not None else None, inv_w, opt.lr, opt.momentum, first)
+        self._after_update(sync, sh_full, ev0, t0)
+        if phases:
+            marks.append(self._comm_events[-1][1])
+            self._phase_marks = marks
 
     def _sync_on_device(self) -> torch.Tensor:
         if not self.offload_snapshot:

@@ -90,6 +90,9 @@ class ModuleDiloco:
                  inner_steps: int = 100, outer_steps: int = 10, comm_dtype: Optional[torch.dtype] = None,
                  offload_snapshot: bool = False, bucket_mb: float = 128.0, max_grad_norm: float = 1.0,
                  broadcast_init: bool = True):
+        if comm_dtype in ("int8", "int4", torch.int8):
+            raise ValueError("quantised transport (comm_dtype int8 / int4) needs the flat-store Llama of Diloco: "
+                             "ModuleDiloco carries fp32 / bf16 pseudo-gradients only")
         self.model = model
         self.inner_optimizer = inner_optimizer
         self.outer_optimizer = outer_optimizer

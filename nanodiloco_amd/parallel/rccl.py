@@ -75,6 +75,7 @@ def lib() -> ctypes.CDLL:
                     "nd_comm_all_reduce": [P, P, P, SZ, I, I, P, ctypes.POINTER(L64)],
                     "nd_comm_broadcast": [P, P, SZ, I, I, P, ctypes.POINTER(L64)],
                     "nd_comm_all_gather": [P, P, SZ, I, P, ctypes.POINTER(L64)],
+                    "nd_comm_all_to_all": [P, P, P, SZ, I, P, ctypes.POINTER(L64)],
                     "nd_comm_wait": [P, L64, P],
                     "nd_comm_query": [P, L64],
                     "nd_comm_error": [P],
@@ -165,6 +166,19 @@ class RcclCommunicator:
         return self._issue("all_gather", out, lambda tk: lib().nd_comm_all_gather(
             self._h, ctypes.c_void_p(out.data_ptr()), out.numel() // self.size, _DTYPES[out.dtype], _stream(self.device),
             tk))
+
+    def all_to_all(self, send: torch.Tensor, recv: torch.Tensor) -> int:
+        """Out of place: piece p of ``send.view(size, -1)`` goes to member p, which stores the piece it gets
+        from member r at ``recv.view(size, -1)[r]``.  Both buffers must outlive the collective."""
+        if send.numel() % self.size or recv.numel() != send.numel() or recv.dtype != send.dtype:
+            raise ValueError("all_to_all: send / recv must match and divide by the group size")
+        if send.data_ptr() == recv.data_ptr():
+            raise ValueError("all_to_all is out of place")
+        if not recv.is_contiguous() or recv.device != self.device:
+            raise ValueError(f"all_to_all: needs a contiguous tensor on {self.device}")
+        return self._issue("all_to_all", send, lambda tk: lib().nd_comm_all_to_all(
+            self._h, ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()), send.numel() // self.size,
+            _DTYPES[send.dtype], _stream(self.device), tk))
 
     def _issue(self, what, t, fn) -> int:
         if not t.is_contiguous() or t.device != self.device:

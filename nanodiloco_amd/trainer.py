@@ -60,7 +60,7 @@ class TrainArgs:
     outer_momentum: float = 0.9
     max_grad_norm: float = 1.0
     weight_decay: float = 0.01
-    comm_dtype: str = "fp32"
+    comm_dtype: str = "fp32"       # fp32 | bf16 | int8 | int4 (block-quantised outer transport, parallel/diloco.py)
     bucket_mb: float = 128.0
     overlap_outer: bool = False
     offload_snapshot: bool = False
@@ -107,6 +107,12 @@ def _dtype(name: str, device: torch.device) -> torch.dtype:
         return torch.bfloat16 if device.type == "cuda" else torch.float32
     return {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16,
             "bfloat16": torch.bfloat16, "fp8": torch.bfloat16}[name]
+
+
+def _comm_dtype(name: str, device: torch.device):
+    """``--comm-dtype``: fp32 | bf16 (a torch dtype, all-reduced) or int8 | int4 (block-quantised transport;
+    int4 has no torch dtype, so both travel as the string)."""
+    return name if name in ("int8", "int4") else _dtype(name, device)
 
 
 def _residual_dtype(name: str, fp8: bool = False) -> torch.dtype:
@@ -200,7 +206,7 @@ class Trainer:
                           skip_nonfinite=a.skip_nonfinite)
         outer = FlatOuterNesterov(self.model.store, lr=a.outer_lr, momentum=a.outer_momentum)
         self.diloco = Diloco(self.model, inner, outer, a.warmup_steps, a.total_steps, a.inner_steps, self.outer_steps,
-                             env=e, comm_dtype=_dtype(a.comm_dtype, e.device), bucket_mb=a.bucket_mb,
+                             env=e, comm_dtype=_comm_dtype(a.comm_dtype, e.device), bucket_mb=a.bucket_mb,
                              overlap=a.overlap_outer, offload_snapshot=a.offload_snapshot,
                              debug_checks=a.debug_checks)
         self.inner_sync = InnerGradSync(self.model, self.diloco.inner_comm)
