@@ -25,22 +25,11 @@
 // one column spread over the banks; transposed reads compute the same swizzled addresses per lane.
 // Causal: tiles past the diagonal are never loaded; fully masked (wave, tile) pairs are skipped;
 // the longest query / key blocks are dispatched first.
-#include "common.h"
+#include "lds_dma.h"
 #include <cstdlib>
 #include <type_traits>
 
 using namespace nd;
-
-typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
-typedef short sv4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bfv8, a), __builtin_bit_cast(bfv8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ sv4 tr_read(const bf16_t* lds_ptr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((sv4 __attribute__((address_space(3)))*)(lds_ptr));
-}
 
 __device__ __forceinline__ bf16x8 cat4(sv4 a, sv4 b) {
   bf16x8 r;
@@ -387,19 +376,10 @@ __device__ __forceinline__ void store_T(bf16_t* out_row, f32x16* acc, float mul,
 }
 
 namespace {
-__device__ __forceinline__ void adma_b128(const void* sbase, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
 __device__ __forceinline__ void adma_b32(const void* sbase, uint32_t voff, uint32_t lds) {
   uint32_t keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-template <class T_>
-__device__ __forceinline__ uint32_t lds_addr(const T_* p) {
-  return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) T_*)p);
 }
 }  // namespace
 
@@ -423,7 +403,7 @@ struct TileDma {
   // rows row0.. of `base` (already offset to the tile's first row) -> LDS tile at byte address `lds`
   __device__ __forceinline__ void issue(const bf16_t* base, uint32_t lds) const {
 #pragma unroll
-    for (int i = 0; i < IPW; ++i) adma_b128(base, voff[i], lds + (uint32_t)((wu + NW * i) * 1024));
+    for (int i = 0; i < IPW; ++i) gdma(base, voff[i], lds + (uint32_t)((wu + NW * i) * 1024));
   }
 };
 
@@ -1287,8 +1267,6 @@ __global__ void __launch_bounds__(256) attn_neg_stats_kernel(const float* __rest
 // ABL (timing ablations, wrong results; ND_ATTN_DKDV_ABL): 1 no Q / dO / statistics DMA and no vmcnt wait,
 // 2 no barrier, 4 no softmax VALU (P = S, dS = dP), 8 no S / dP MFMAs, 16 no dV / dK MFMAs, 32 LDS fragments
 // read only in the first step
-template <int N> __device__ __forceinline__ void dkdv_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-
 // NB: Q / dO / statistics buffers in LDS; tile it + NB - 1 is in flight while tile it is computed
 template <int HD, bool ROPE_OUT, int BQ = 64, bool PAD = false, int NW = 4, int ABL = 0, int NB = 2>
 __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 64 && (ND_ATTN_X & 64)) ? 3 : 2)) attn_bwd_dkdv_dma_kernel(
@@ -1374,8 +1352,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
       const uint32_t off = (uint32_t)(buf * BQ * HD * 2 + (wu + NW * i) * 1024);
-      if (part & 1) adma_b128(sq, vq[i], qs_a + off);
-      if (part & 2) adma_b128(sd, vd[i], do_a + off);
+      if (part & 1) gdma(sq, vq[i], qs_a + off);
+      if (part & 2) gdma(sd, vd[i], do_a + off);
     }
     ND_STAMP(stp.mark(9);)
     if ((part & 4) && wu < BQ / 64) {  // one 64-float wave-instruction per 64 rows
@@ -1397,13 +1375,13 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
       if constexpr (NB > 2) {
         constexpr int PT = 2 * IPW;  // per tile and wave, plus 2 statistics loads on waves < BQ / 64
         if (it + NB - 2 < nit) {
-          if (wu < BQ / 64) dkdv_vm<(PT + 2) * (NB - 2)>();
-          else dkdv_vm<PT * (NB - 2)>();
+          if (wu < BQ / 64) vmwait<(PT + 2) * (NB - 2)>();
+          else vmwait<PT * (NB - 2)>();
         } else {
-          dkdv_vm<0>();
+          vmwait<0>();
         }
       } else {
-        dkdv_vm<0>();
+        vmwait<0>();
       }
     }
     ND_STAMP(stp.mark(0);)

@@ -62,14 +62,13 @@
 //
 // Reference role: every nn.Linear of HF LlamaForCausalLM (/root/reference/nanodiloco/main.py:97-99,
 // run at :109-111).
-#include "common.h"
+#include "lds_dma.h"
 #include <cstdlib>
 #include <type_traits>
 
 using namespace nd;
 
 namespace {
-typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
 constexpr int TM = 256, TN = 256, TK = 64;
 constexpr uint32_t HALF_B = 128 * TK * 2;  // bytes of one half-tile (16 KiB)
 constexpr uint32_t BUF_B = 4 * HALF_B;     // bytes of one K-tile buffer (64 KiB)
@@ -104,23 +103,6 @@ template <int EPI> struct NStores { static constexpr int v = EPI == PP_SWIGLU ? 
 #define DSW_PF 6  // PP_DSWIGLU epilogue: gate / up load steps in flight
 #endif
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-// one LDS-DMA wave-instruction: 64 lanes x 16 B from descriptor r at per-lane byte offset voff to
-// LDS [lds, lds + 1 KiB); lanes past the descriptor's record count read nothing (tail rows)
-__device__ __forceinline__ void dma(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(r), "s"(lds) : "memory");
-}
-// FLAT-global form (SGPR base + 32-bit per-lane offset, no range check): the default for half-tiles whose rows
-// all exist (tail half-tiles keep the range-checked buffer form)
-__device__ __forceinline__ void gdma(const void* base, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(lds) : "memory");
-}
 // accumulator pinned to AGPRs (tied operand): the chain on one accumulator needs no wait states;
 // compiler code reading the result waits for drain()
 #ifndef ND_PP_ASM_MFMA
@@ -159,14 +141,6 @@ __device__ __forceinline__ void mma8z(const i32x8& b, const i32x8& a, f32x4& c, 
                                                          one);
 }
 __device__ __forceinline__ void drain() { asm volatile("s_nop 15\n\ts_nop 3" ::: "memory"); }
-__device__ __forceinline__ void bar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
-template <int N> __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
 // runtime count out of a small compile-time set (wave-uniform branch)
 template <int NST> __device__ __forceinline__ void vmwait_n(int n) {
   switch (n) {

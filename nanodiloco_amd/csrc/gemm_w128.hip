@@ -35,30 +35,19 @@
 //
 // Reference role: every nn.Linear of HF LlamaForCausalLM (/root/reference/nanodiloco/main.py:97-99,
 // run at :109-111).
-#include "common.h"
+#include "lds_dma.h"
 #include <cstdlib>
 #include <type_traits>
 
 using namespace nd;
 
 namespace {
-typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
 constexpr int TM = 256, TN = 256, TK = 64;
 constexpr uint32_t BUFB0 = 2 * 256 * 128;  // one K-tile buffer (A + B, 64 KiB) without padding
 constexpr int LGKM0 = 0xC07F;        // s_waitcnt lgkmcnt(0), vmcnt / expcnt at their maxima
 
 enum : int { W_STORE = 0 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-// one LDS-DMA wave-instruction: 64 lanes x 16 B from descriptor r at per-lane byte offset voff to LDS
-// [lds, lds + 1 KiB); lanes past the descriptor's record count read nothing
-__device__ __forceinline__ void dma(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(r), "s"(lds) : "memory");
-}
 // m0 set one MFMA ahead of its piece (nothing else in these kernels reads m0), then the bare load
 __device__ __forceinline__ void set_m0(uint32_t lds) { asm volatile("s_mov_b32 m0, %0" ::"s"(lds) : "memory"); }
 __device__ __forceinline__ void dma_go(__amdgpu_buffer_rsrc_t r, uint32_t voff) {
@@ -68,14 +57,6 @@ __device__ __forceinline__ void dma_go(__amdgpu_buffer_rsrc_t r, uint32_t voff) 
 __device__ __forceinline__ void gdma_go(const void* sbase, uint32_t voff) {
   asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase) : "memory");
 }
-__device__ __forceinline__ void bar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
-template <int N> __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
 template <int ABL, int N> __device__ __forceinline__ void vmwait_l() {
   if constexpr ((ABL & 16) == 0) vmwait<N>();
 }

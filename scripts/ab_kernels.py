@@ -9,7 +9,11 @@ compared inside one process, alternating).
 --what attn : attention fwd+bwd on the Llama-150M micro-batch (per-kernel times via torch.profiler
               are not needed: each op is timed with HIP events, min over rounds)
 --what step : one full forward+backward of Llama-150M (micro-batch 32 x 1024)
---what wgrad: the wgrad GEMM shapes
+--what wgrad: the wgrad GEMM shapes (bf16, and the fp8 weight gradient at the same shapes)
+--what wgradk: small weight-gradient shapes that reach every kernel of csrc/gemm_wgrad.hip and every edge of the
+              ping-pong pipeline (1 / 2 / 3 K-tiles, split-K, partial tiles); outputs compared bitwise.  The
+              shape set follows ND_WGRAD_VARIANT (read once per process): "" all kernels, "b" the ping-pong
+              shapes, "dma0" / "dmas" one LDS-DMA-kernel shape
 --what epi  : the fused-epilogue ping-pong GEMMs (q|k|v+RoPE, gate|up+SwiGLU, down dgrad+SwiGLU bwd)
 """
 import argparse
@@ -124,6 +128,7 @@ def workloads(what):
         out["cast_e5m2"] = cast
         OUTPUTS["cast_e5m2"] = (q8,)
     elif what == "wgrad":
+        from nanodiloco_amd.ops import gemm as G
         from nanodiloco_amd.ops.gemm import wgrad
         # lm: 500 output tiles -> one split (C += acc in place, the S == 1 epilogue)
         for name, (M, N) in {"qkv": (3072, 1024), "o": (1024, 1024), "gate_up": (5376, 1024),
@@ -132,13 +137,60 @@ def workloads(what):
             xx = torch.randn(32768, N, device="cuda").bfloat16()
             gw = torch.zeros(M, N, device="cuda")
             out[name] = (lambda gw=gw, dy=dy, xx=xx: wgrad(gw, dy, xx))
+            dy8, xx8 = dy.to(torch.float8_e5m2), xx.to(torch.float8_e4m3fn)
+            one = torch.ones(1, device="cuda")
+            out[name + "_f8"] = (lambda gw=gw, dy8=dy8, xx8=xx8, one=one: G.wgrad_f8(gw, dy8, xx8, one, one))
+    elif what == "wgradk":
+        from nanodiloco_amd.ops import gemm as G
+        variant = os.environ.get("ND_WGRAD_VARIANT", "")
+        pp = [(1024, 512, 64), (1024, 512, 128), (1024, 512, 192), (1024, 512, 512), (1000, 520, 41 * 64)]
+        if variant in ("dma0", "dmas"):
+            bf16, grouped, f8 = [(1024, 512, 256)], [], []
+        elif variant == "b":
+            bf16, grouped, f8 = pp, [], []
+        else:
+            bf16 = [(128, 512, 64), (1000, 264, 777), (1024, 512, 200), (1000, 520, 777)] + pp
+            grouped = [(((1000, 1032), (520, 2048)), 41 * 64)]
+            f8 = [(256, 256, 128), (1024, 512, 128), (1024, 512, 256), (1024, 512, 384), (1008, 528, 41 * 128)]
+
+        def operands(M, N, K):
+            return (torch.randn(K, M, device="cuda"), torch.randn(K, N, device="cuda"),
+                    torch.randn(M, N, device="cuda"), torch.empty(M, N, device="cuda"))
+
+        # every call starts from the same random C (no accumulation across calls): the two libraries' outputs
+        # are then comparable bit for bit
+        for M, N, K in bf16:
+            dy, xx, c0, gw = operands(M, N, K)
+            dy, xx = dy.bfloat16(), xx.bfloat16()
+            name = f"bf16_{M}x{N}x{K}"
+            out[name] = (lambda gw=gw, c0=c0, dy=dy, xx=xx: (gw.copy_(c0), G.wgrad(gw, dy, xx)))
+            OUTPUTS[name] = (gw,)
+        for ((M0, N0), (M1, N1)), K in grouped:
+            dy0, x0, c0, g0 = operands(M0, N0, K)
+            dy1, x1, c1, g1 = operands(M1, N1, K)
+            dy0, x0, dy1, x1 = dy0.bfloat16(), x0.bfloat16(), dy1.bfloat16(), x1.bfloat16()
+
+            def pair(g0=g0, g1=g1, c0=c0, c1=c1, dy0=dy0, x0=x0, dy1=dy1, x1=x1):
+                g0.copy_(c0), g1.copy_(c1)
+                assert G.wgrad2(g0, dy0, x0, g1, dy1, x1)
+            out["grouped"] = pair
+            OUTPUTS["grouped"] = (g0, g1)
+        for M, N, K in f8:
+            for fmt, dt in (("e5m2", torch.float8_e5m2), ("e4m3", torch.float8_e4m3fn)):
+                dy, xx, c0, gw = operands(M, N, K)
+                dy8, xx8 = dy.to(dt), xx.to(torch.float8_e4m3fn)
+                sa, sb = torch.full((1,), 0.37, device="cuda"), torch.full((1,), 1.9, device="cuda")
+                name = f"{fmt}_{M}x{N}x{K}"
+                out[name] = (lambda gw=gw, c0=c0, dy8=dy8, xx8=xx8, sa=sa, sb=sb:
+                             (gw.copy_(c0), G.wgrad_f8(gw, dy8, xx8, sa, sb)))
+                OUTPUTS[name] = (gw,)
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--alt", required=True)
-    ap.add_argument("--what", default="attn", choices=["attn", "attnk", "step", "wgrad", "ce", "epi", "cast"])
+    ap.add_argument("--what", default="attn", choices=["attn", "attnk", "step", "wgrad", "wgradk", "ce", "epi", "cast"])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     a = ap.parse_args()
@@ -164,7 +216,7 @@ def main():
             same = " | bitwise " + ("equal" if all(torch.equal(a, b) for a, b in zip(mine, OUTPUTS[k])) else
                                     "DIFFERENT (max %.3g)" % max((a.float() - b.float()).abs().max().item()
                                                                  for a, b in zip(mine, OUTPUTS[k])))
-        print(f"{k:10s} working-tree {n:9.1f} us | alt {o:9.1f} us | speedup {o / n:5.3f}x{same}", flush=True)
+        print(f"{k:22s} working-tree {n:9.1f} us | alt {o:9.1f} us | speedup {o / n:5.3f}x{same}", flush=True)
     del base
 
 

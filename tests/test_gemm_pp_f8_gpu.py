@@ -139,7 +139,8 @@ def test_gemm_pp_f8_deterministic():
 
 # ---------------------------------------------------------------- fp8 weight gradient (wgrad8_pp_kernel)
 WG_SHAPES = [(256, 256, 128), (1024, 1024, 4096), (3072, 1024, 8192), (1024, 2688, 2048), (5376, 1024, 4096),
-             (1000 // 16 * 16, 528, 1024), (2688, 1024, 384), (256, 32000 // 16 * 16, 256)]
+             (1000 // 16 * 16, 528, 1024), (2688, 1024, 384), (256, 32000 // 16 * 16, 256),
+             (1024, 512, 128), (1024, 512, 384)]  # short K, 8 tiles: the pipeline's prologue with no steady state
 
 
 @pytest.mark.parametrize("ddt", [E5, E4], ids=["e5m2", "e4m3"])
