@@ -385,25 +385,34 @@ __device__ __forceinline__ void adma_b32(const void* sbase, uint32_t voff, uint3
 
 // LDS-DMA of one ROWS x HD bf16 tile (row stride ld) into a soff<HD>-swizzled LDS tile by the 4 waves
 // of a workgroup: 1-KiB wave-instructions of 64/CPR rows, per-lane source offsets fixed per kernel.
-template <int HD, int ROWS, int NW = 4>  // NW waves share the tile
+// ONE (the document-mask kernels, which have no register to spare next to their pad counterparts): a wave's
+// pieces lie NW * RPI rows apart, a multiple of the swizzle's 16-row period, so they share one per-lane offset
+// and the row step goes into the scalar base instead of IPW offsets held in VGPRs.
+template <int HD, int ROWS, int NW = 4, bool ONE = false>  // NW waves share the tile
 struct TileDma {
   static constexpr int CPR = HD / 8, RPI = 64 / CPR, IPW = (ROWS / RPI) / NW;
-  uint32_t voff[IPW];
+  static_assert(!ONE || (NW * RPI) % 16 == 0, "pieces of one wave must share the swizzle phase");
+  uint32_t voff[ONE ? 1 : IPW];
+  int64_t step;  // ONE: elements between the first rows of a wave's consecutive pieces
   int wu;
   __device__ __forceinline__ void init(int64_t ld) {
     const int lane = threadIdx.x & 63;
     wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #pragma unroll
-    for (int i = 0; i < IPW; ++i) {
+    for (int i = 0; i < (ONE ? 1 : IPW); ++i) {
       const int row = (wu + NW * i) * RPI + lane / CPR, p = lane % CPR;
       const int lch = (soff<HD>(row, p * 8) - row * HD) / 8;  // XOR swizzle: physical p holds logical lch
       voff[i] = (uint32_t)(((int64_t)row * ld + lch * 8) * 2);
     }
+    if constexpr (ONE) step = (int64_t)(NW * RPI) * ld;
   }
   // rows row0.. of `base` (already offset to the tile's first row) -> LDS tile at byte address `lds`
   __device__ __forceinline__ void issue(const bf16_t* base, uint32_t lds) const {
 #pragma unroll
-    for (int i = 0; i < IPW; ++i) gdma(base, voff[i], lds + (uint32_t)((wu + NW * i) * 1024));
+    for (int i = 0; i < IPW; ++i) {
+      if constexpr (ONE) gdma(base + i * step, voff[0], lds + (uint32_t)((wu + NW * i) * 1024));
+      else gdma(base, voff[i], lds + (uint32_t)((wu + NW * i) * 1024));
+    }
   }
 };
 
@@ -419,7 +428,37 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // correct variant (cheaper mask, max tree, split row sum: needs T % 64 == 0), the default of the
 // LDS-DMA path since the tile loop is unrolled (ND_ATTN_ABL=0 for the plain one).
 // NW: waves per workgroup (4 or 8; 8 = 256-query blocks, every K/V tile DMA'd once per 256 queries: DMA only)
-template <int HD, bool ROPE, bool DMA = false, bool PAD = false, int ABL = 0, int NW = 4>  // DMA: LDS-DMA K/V staging (!ROPE, T % 64 == 0)
+// MASK: what KS holds besides the causal mask.  MASK_NONE: nothing.  MASK_PAD: per-sequence key start [B] (left
+// padding).  MASK_DOC (LDS-DMA kernels only): per-token bounds [B, T] of the token's document in a packed window --
+// doc_start for the query-parallel kernels (query q sees keys doc_start[q] <= k <= q), doc_end for dK/dV (key k is
+// seen by queries k <= q < doc_end[k]).  doc_start is non-decreasing, so a block's / wave's first query carries its
+// minimum: 64-key tiles wholly before it are neither loaded (block) nor multiplied (wave).
+constexpr int MASK_NONE = 0, MASK_PAD = 1, MASK_DOC = 2;
+// MASK_DOC keeps no per-lane bound live across the tile loop (the head_dim-64 forward and dK/dV kernels sit exactly
+// on their register budgets): a wave's 32 rows are consecutive tokens, so their bounds are the bound of the
+// document that is open at the wave's edge (one scalar) plus one bit per row -- "a document starts / ends here" --
+// in a 32-bit scalar mask.  The few tiles that hold a boundary rebuild the lane's bound from the two.
+struct DocWave {
+  int edge;       // doc_start of the wave's first row / doc_end of its last row
+  uint32_t bits;  // bit i: row i of the wave starts (doc_start == row) / ends (doc_end == row + 1) a document
+  // doc_start of row (row0 + i): the last start at or before it
+  __device__ __forceinline__ int start_of(int row0, int i) const {
+    const uint32_t m = bits & (0xffffffffu >> (31 - i));
+    return m ? row0 + 31 - __builtin_clz(m | 1u) : edge;  // | 1: no clz(0); m != 0 keeps its top bit
+  }
+  // doc_end of row (row0 + i): one past the first end at or after it
+  __device__ __forceinline__ int end_of(int row0, int i) const {
+    const uint32_t m = bits >> i;
+    return m ? row0 + i + __builtin_ctz(m | 0x80000000u) + 1 : edge;  // no ctz(0); m != 0 keeps its low bit
+  }
+};
+// Bits [lo, hi) of a 32-bit word, for any lo / hi (empty when hi <= lo): a lane's visible rows of a 32-row
+// sub-tile as ONE register, tested against immediates -- a two-sided bound would hold two.
+__device__ __forceinline__ uint32_t bit_range(int lo, int hi) {
+  const int l = min(max(lo, 0), 32), u = min(max(hi, 0), 32);
+  return (uint32_t)((1ull << u) - 1) & (uint32_t)(~0ull << l);
+}
+template <int HD, bool ROPE, bool DMA = false, int MASK = MASK_NONE, int ABL = 0, int NW = 4>  // DMA: LDS-DMA K/V staging (!ROPE, T % 64 == 0)
 __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && !(ND_ATTN_X & 32)) ? 4 : 3)) attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
                                                           float* __restrict__ LSE, int B, int nh, int nkv, int T,
@@ -427,6 +466,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
                                                           const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                           const int* __restrict__ KS, float thr, int order) {
   constexpr int BN = 64, NT = HD / 16, NO = HD / 32;
+  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC;
+  static_assert(!DOC || (DMA && ABL == 0 && NW == 4), "document mask: default LDS-DMA kernel, plain softmax variant");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * BN * HD];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[2 * BN * HD];
 
@@ -452,7 +493,18 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
   const int ks = PAD ? KS[b] : 0;  // PAD (left-padded batch): keys < ks are masked for every query
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c32 = lane & 31;
   const int g = lane >> 4, i16 = lane & 15;
-  const int q0w = qb * QB + w * 32, qi = q0w + c32;
+  // DOC: the wave's first query as a scalar, so that the per-tile skip / boundary tests are scalar branches
+  const int q0w = qb * QB + (DOC ? __builtin_amdgcn_readfirstlane(w) : w) * 32, qi = q0w + c32;
+  // DOC: dsw0 / dsw1 = document start of the wave's first / last query (the wave's minimum / maximum)
+  int dsw0 = 0, dsw1 = 0;
+  DocWave dw{0, 0};
+  if constexpr (DOC) {
+    const int ds = qi < T ? KS[(int64_t)b * T + qi] : 0;
+    dsw0 = __builtin_amdgcn_readfirstlane(ds);
+    dsw1 = __builtin_amdgcn_readlane(ds, 31);
+    dw.edge = dsw0;
+    dw.bits = (uint32_t)__builtin_amdgcn_ballot_w64(ds == qi);  // lanes l and l + 32 hold the same row
+  }
   const float c = scale * LOG2E;
   const bf16_t* Qb = Q + (int64_t)b * T * ld + (int64_t)head * HD;
   const bf16_t* Kb = K + (int64_t)b * T * ld + (int64_t)kvh * HD;
@@ -469,20 +521,24 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
   float m = -INFINITY, l = 0.f;
 
   const int ntiles = (min(T, qb * QB + QB) + BN - 1) / BN;
+  // DOC: the first tile that holds a key of the block's first query's document (clamped: bounds that break the
+  // doc_start[t] <= t invariant must not move the loads out of the sequence); the buffer parity counts from it
+  int j0 = 0;
+  if constexpr (DOC) j0 = min(max(__builtin_amdgcn_readfirstlane(KS[(int64_t)b * T + qb * QB]), 0) / BN, ntiles - 1);
   typename std::conditional<ROPE, StageRope<BN, HD>, Stage<BN, HD>>::type sk;
   Stage<BN, HD> sv;
-  TileDma<HD, BN, NW> tdma;
+  TileDma<HD, BN, NW, DOC> tdma;
   const uint32_t ks_a = lds_addr(Ks), vs_a = lds_addr(Vs);
-  auto dma_issue = [&](int j) {
-    const uint32_t off = (uint32_t)((j & 1) * BN * HD * 2);
+  auto dma_issue = [&](int j, int par) {
+    const uint32_t off = (uint32_t)(par * BN * HD * 2);
     tdma.issue(Kb + (int64_t)j * BN * ld, ks_a + off);
     tdma.issue(Vb + (int64_t)j * BN * ld, vs_a + off);
   };
   ND_STAMP(Stamps stp; stp.start();)
   if constexpr (DMA) {
-    // double-buffered tiles: wait(tile j) + barrier | DMA tile j+1 -> buf (j+1)&1 | compute(buf j&1)
+    // double-buffered tiles: wait(tile j) + barrier | DMA tile j+1 -> buf PAR^1 | compute(buf PAR), PAR = (j-j0)&1
     tdma.init(ld);
-    dma_issue(0);
+    dma_issue(j0, 0);
   } else {
     // double-buffered tiles: compute(buf j&1) | regs hold tile j+1 | store -> buf (j+1)&1 | ONE barrier
     load_tile<ROPE>(sk, Kb, ld, 0, T, cosT, sinT);
@@ -511,10 +567,11 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
       ND_STAMP(stp.mark(0);)
       if constexpr (!(ABL & 2)) __syncthreads();
       ND_STAMP(stp.mark(1);)
-      if constexpr (!(ABL & 1)) if (j + 1 < ntiles) dma_issue(j + 1);
+      if constexpr (!(ABL & 1)) if (j + 1 < ntiles) dma_issue(j + 1, PAR ^ 1);
       ND_STAMP(stp.mark(2);)
     }
-    if (k0 <= q0w + 31) {  // else: whole tile above this wave's diagonal (wave-uniform)
+    // else: whole tile above this wave's diagonal, or (DOC) before its first query's document (wave-uniform)
+    if (k0 <= q0w + 31 && (!DOC || k0 + BN > dsw0)) {
       // K row fragments issued up front (V^T transposing reads stay next to their MFMAs: holding
       // them too costs the third wave per SIMD)
       bf16x8 ka[2][NT];
@@ -586,7 +643,19 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
         }
         mx = pair_max32(max3f(a4[0], a4[1], max3f(a4[2], a4[3], a4[3]))) * c;
       } else {
-        if ((k0 + BN - 1 > q0w) || (k0 + BN > T) || (PAD && k0 < ks)) {
+        if constexpr (DOC) {
+          if ((k0 + BN - 1 > q0w) || k0 < dsw1) {
+            // doc_start <= key <= qi (T % 64 == 0: no key >= T)
+            const int ds = dw.start_of(q0w, c32);
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+              const uint32_t vis = bit_range(ds - k0 - kt * 32, qi + 1 - k0 - kt * 32) >> (4 * h);
+#pragma unroll
+              for (int r = 0; r < 16; ++r)
+                if (!(vis & (1u << ((r & 3) + 8 * (r >> 2))))) s[kt][r] = -INFINITY;
+            }
+          }
+        } else if ((k0 + BN - 1 > q0w) || (k0 + BN > T) || (PAD && k0 < ks)) {
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -607,8 +676,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
       // Both lanes of a query pair see the same m / mx, so l and O get one consistent factor.
       const bool upd = mx > m + thr;
       const float mnew = upd ? mx : m;
-      // a row with no visible key yet (a left-pad query: every key masked) keeps p = 0, l = 0
-      const float mref = (PAD && mnew == -INFINITY) ? 0.f : mnew;
+      // a row with no visible key yet (a left-pad query, or a tile before the query's document: every key
+      // masked) keeps p = 0, l = 0
+      const float mref = (MASK != MASK_NONE && mnew == -INFINITY) ? 0.f : mnew;
       const float alpha = upd ? fexp2(m - mref) : 1.f;
       m = mnew;
       float rs4[4] = {0.f, 0.f, 0.f, 0.f};  // variant 32: four independent partial sums
@@ -682,7 +752,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
     }
     };
   if constexpr (DMA) {
-    for (int j = 0; j < ntiles; j += 2) {
+    for (int j = j0; j < ntiles; j += 2) {
       tile(j, std::integral_constant<int, 0>{});
       if (j + 1 < ntiles) tile(j + 1, std::integral_constant<int, 1>{});
     }
@@ -692,7 +762,16 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
   ND_STAMP(stp.mark(7);)
   const float lt = pair_sum32(l);
   const float inv = lt > 0.f ? 1.f / lt : 0.f;
-  if (qi < T) {
+  if constexpr (DOC) {
+    // the lane's row and half taken afresh from the lane id: the prologue's copies (a 64-bit row index, the lane
+    // id) would otherwise be held, or spilled, across the whole tile loop for these few stores
+    const int le = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int qe = q0w + (le & 31), he = le >> 5;
+    if (qe < T) {
+      store_T<HD>(O + ((int64_t)b * T + qe) * ldo + (int64_t)head * HD, oacc, inv, he, nullptr, nullptr, 0);
+      if (he == 0) LSE[((int64_t)b * nh + head) * T + qe] = m + log2f(lt);
+    }
+  } else if (qi < T) {
     store_T<HD>(O + ((int64_t)b * T + qi) * ldo + (int64_t)head * HD, oacc, inv, h, nullptr, nullptr, 0);
     if (h == 0) LSE[((int64_t)b * nh + head) * T + qi] = m + log2f(lt);
   }
@@ -738,7 +817,7 @@ __global__ void __launch_bounds__(256) attn_bwd_pre_kernel(const bf16_t* __restr
 #ifndef ND_ATTN_DQ_OCC
 #define ND_ATTN_DQ_OCC 2  // waves / SIMD the head_dim-64 dQ kernel is compiled for (A/B)
 #endif
-template <int HD, bool ROPE, bool ROPE_OUT, bool DMA = false, bool PRE = false, bool PAD = false, int NW = 4>  // DMA: LDS-DMA K/V staging
+template <int HD, bool ROPE, bool ROPE_OUT, bool DMA = false, bool PRE = false, int MASK = MASK_NONE, int NW = 4>  // DMA: LDS-DMA K/V staging; MASK: see attn_fwd_kernel
 __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_DQ_OCC : 2)) attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                              const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
                                                              const float* __restrict__ LSE, const float* __restrict__ DELTA,
@@ -750,6 +829,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
                                                              float* __restrict__ ND = nullptr,
                                                              const int* __restrict__ KS = nullptr, int order = 0) {
   constexpr int BN = 64, NT = HD / 16, NO = HD / 32;
+  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC;
+  static_assert(!DOC || (DMA && PRE), "document mask: fused LDS-DMA backward only");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * BN * HD];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[2 * BN * HD];
 
@@ -771,7 +852,16 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
   const int ks = PAD ? KS[b] : 0;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c32 = lane & 31;
   const int g = lane >> 4, i16 = lane & 15;
-  const int q0w = qb * QB + w * 32, qi = q0w + c32;
+  const int q0w = qb * QB + (DOC ? __builtin_amdgcn_readfirstlane(w) : w) * 32, qi = q0w + c32;
+  int dsw0 = 0, dsw1 = 0;  // see attn_fwd_kernel
+  DocWave dw{0, 0};
+  if constexpr (DOC) {
+    const int ds = qi < T ? KS[(int64_t)b * T + qi] : 0;
+    dsw0 = __builtin_amdgcn_readfirstlane(ds);
+    dsw1 = __builtin_amdgcn_readlane(ds, 31);
+    dw.edge = dsw0;
+    dw.bits = (uint32_t)__builtin_amdgcn_ballot_w64(ds == qi);
+  }
   const float c = scale * LOG2E;
   const bf16_t* Qb = Q + (int64_t)b * T * ld + (int64_t)head * HD;
   const bf16_t* dOb = dO + (int64_t)b * T * ldo + (int64_t)head * HD;
@@ -815,18 +905,20 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
   for (int o = 0; o < NO; ++o) dq[o] = f32x16{};
 
   const int ntiles = (min(T, qb * QB + QB) + BN - 1) / BN;
+  int j0 = 0;  // see attn_fwd_kernel
+  if constexpr (DOC) j0 = min(max(__builtin_amdgcn_readfirstlane(KS[(int64_t)b * T + qb * QB]), 0) / BN, ntiles - 1);
   typename std::conditional<ROPE, StageRope<BN, HD>, Stage<BN, HD>>::type sk;
   Stage<BN, HD> sv;
-  TileDma<HD, BN, NW> tdma;
+  TileDma<HD, BN, NW, DOC> tdma;
   const uint32_t ks_a = lds_addr(Ks), vs_a = lds_addr(Vs);
   auto dma_issue = [&](int j) {
-    const uint32_t off = (uint32_t)((j & 1) * BN * HD * 2);
+    const uint32_t off = (uint32_t)(((j - j0) & 1) * BN * HD * 2);
     tdma.issue(Kb + (int64_t)j * BN * ld, ks_a + off);
     tdma.issue(Vb + (int64_t)j * BN * ld, vs_a + off);
   };
   if constexpr (DMA) {
     tdma.init(ld);
-    dma_issue(0);
+    dma_issue(j0);
   } else {
     load_tile<ROPE>(sk, Kb, ld, 0, T, cosT, sinT);
     sv.load(Vb, ld, 0, T);
@@ -839,10 +931,10 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
     }
   }
   ND_STAMP(stp.mark(9);)
-  for (int j = 0; j < ntiles; ++j) {
+  for (int j = j0; j < ntiles; ++j) {
     const int k0 = j * BN;
-    const bf16_t* Kt = Ks + (j & 1) * (BN * HD);
-    const bf16_t* Vt = Vs + (j & 1) * (BN * HD);
+    const bf16_t* Kt = Ks + ((j - j0) & 1) * (BN * HD);
+    const bf16_t* Vt = Vs + ((j - j0) & 1) * (BN * HD);
     if constexpr (DMA) {
       ND_STAMP(stp.mark(7);)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -852,11 +944,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
       if (j + 1 < ntiles) dma_issue(j + 1);
       ND_STAMP(stp.mark(2);)
     }
-    if (k0 <= q0w + 31) {
-      const bool diag = (k0 + BN - 1 > q0w) || (k0 + BN > T) || (qi >= T) || (PAD && k0 < ks);
+    if (k0 <= q0w + 31 && (!DOC || k0 + BN > dsw0)) {  // DOC: else the tile lies before the wave's first document
+      const bool diag = (k0 + BN - 1 > q0w) || (k0 + BN > T) || (qi >= T) || (PAD && k0 < ks) || (DOC && k0 < dsw1);
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         if (k0 + kt * 32 > q0w + 31) continue;  // this 32-key half is above the wave's diagonal
+        if (DOC && k0 + kt * 32 + 32 <= dsw0) continue;  // ... or before the wave's first document
         ND_STAMP(stp.mark(7);)
         // fragments issued up front (row reads for S^T / dP^T, transposing reads for dQ)
         bf16x8 ka[NT], va[NT], tk[2][NO];
@@ -896,6 +989,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
 #pragma unroll
             for (int r = 0; r < 16; ++r) dp[r] = fexp2(fmaf(s[r], c, -lse)) * (dp[r] - dlt);
           }
+        } else if constexpr (DOC) {
+          const int ds = dw.start_of(q0w, c32);
+          const int koff = k0 + kt * 32 + 4 * h - ds;
+          const uint32_t span = qi < T ? (uint32_t)(qi - ds) : 0u;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float p = (uint32_t)(koff + (r & 3) + 8 * (r >> 2)) <= span ? fexp2(fmaf(s[r], c, -lse)) : 0.f;
+            dp[r] = p * (dp[r] - dlt);
+          }
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -919,7 +1021,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
     }
     if constexpr (!DMA) {
       if (j + 1 < ntiles) {
-        sk.store(Ks + ((j + 1) & 1) * (BN * HD));
+        sk.store(Ks + ((j + 1) & 1) * (BN * HD));  // register-staged path: j0 = 0
         sv.store(Vs + ((j + 1) & 1) * (BN * HD));
       }
       __syncthreads();
@@ -1233,6 +1335,33 @@ ND_API int nd_attn_fwd(const void* q, const void* k, const void* v, void* o, flo
   return nd_attn_fwd_ks(q, k, v, o, lse, B, nh, nkv, T, hd, ld, ldo, cosT, sinT, scale, nullptr, s);
 }
 
+// Document-masked forward for packed windows (several documents per sequence): query q attends to keys
+// doc_start[b, q] <= k <= q.  doc_start / doc_end: int32 [B, T] on the device, doc_start non-decreasing and
+// constant inside a document, doc_start[t] <= t < doc_end[t] (ops.doc_bounds builds them from the EOS positions).
+// LDS-DMA kernel only: q|k already rotated (cosT / sinT must be null), T % 64 == 0.  Always the default block
+// shape and the plain softmax variant (as the left-pad mode); the A/B switches of AttnEnv do not apply.
+template <int HD>
+static int fwd_doc_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int nh, int nkv,
+                          int T, int64_t ld, int64_t ldo, float scale, const int* doc_start, hipStream_t s) {
+  hipLaunchKernelGGL((attn_fwd_kernel<HD, false, true, MASK_DOC>), dim3((T + 127) / 128 * B * nh), dim3(256), 0, s,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, B, nh, nkv, T, ld, ldo,
+                     scale, nullptr, nullptr, doc_start, g_attn.thr, attn_order());
+  ND_LAUNCH_CHECK();
+}
+
+ND_API int nd_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, int B, int nh, int nkv,
+                           int T, int hd, int64_t ld, int64_t ldo, const float* cosT, const float* sinT, float scale,
+                           const int* doc_start, const int* doc_end, hipStream_t s) {
+  if (nh % nkv || (ld % 8) || (ldo % 8) || T % 64 || cosT || sinT || !doc_start || !doc_end)
+    return (int)hipErrorInvalidValue;
+  switch (hd) {
+    case 32: return fwd_doc_launch<32>(q, k, v, o, lse, B, nh, nkv, T, ld, ldo, scale, doc_start, s);
+    case 64: return fwd_doc_launch<64>(q, k, v, o, lse, B, nh, nkv, T, ld, ldo, scale, doc_start, s);
+    case 128: return fwd_doc_launch<128>(q, k, v, o, lse, B, nh, nkv, T, ld, ldo, scale, doc_start, s);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
 ND_API int nd_attn_bwd_pre(const void* o, const void* dout, float* delta, int B, int nh, int T, int64_t hd,
                            int64_t ldo, hipStream_t s) {
   const int64_t threads = (int64_t)B * T * nh * (hd / 8);
@@ -1268,7 +1397,8 @@ __global__ void __launch_bounds__(256) attn_neg_stats_kernel(const float* __rest
 // 2 no barrier, 4 no softmax VALU (P = S, dS = dP), 8 no S / dP MFMAs, 16 no dV / dK MFMAs, 32 LDS fragments
 // read only in the first step
 // NB: Q / dO / statistics buffers in LDS; tile it + NB - 1 is in flight while tile it is computed
-template <int HD, bool ROPE_OUT, int BQ = 64, bool PAD = false, int NW = 4, int ABL = 0, int NB = 2>
+// MASK_DOC: KS = doc_end [B, T]; the query-tile walk ends with the document of the block's last key
+template <int HD, bool ROPE_OUT, int BQ = 64, int MASK = MASK_NONE, int NW = 4, int ABL = 0, int NB = 2>
 __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 64 && (ND_ATTN_X & 64)) ? 3 : 2)) attn_bwd_dkdv_dma_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ NL, const float* __restrict__ ND, bf16_t* __restrict__ dK,
@@ -1279,6 +1409,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
   constexpr int RPI = 64 / CPR;            // rows per 1-KiB DMA wave-instruction
   constexpr int IPW = (BQ / RPI) / NW;     // DMA instructions per wave per operand tile
   constexpr int KB = 32 * NW;              // keys per workgroup
+  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC;
   __shared__ __attribute__((aligned(16))) bf16_t Qs[NB * BQ * HD];
   __shared__ __attribute__((aligned(16))) bf16_t dOs[NB * BQ * HD];
   __shared__ __attribute__((aligned(16))) float lse_s[NB * BQ];
@@ -1298,7 +1429,18 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
   const int ks = PAD ? KS[b] : 0;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c32 = lane & 31;
   const int g = lane >> 4, i16 = lane & 15;
-  const int kw0 = kb * KB + w * 32, key = kw0 + c32;
+  const int kw0 = kb * KB + (DOC ? __builtin_amdgcn_readfirstlane(w) : w) * 32, key = kw0 + c32;
+  // DOC: one past the last query that sees this key; dew0 / dew1 = the wave's first / last key's (doc_end is
+  // non-decreasing like doc_start: its minimum / maximum)
+  int dew0 = 0, dew1 = 0;
+  DocWave dw{0, 0};
+  if constexpr (DOC) {
+    const int de = key < T ? KS[(int64_t)b * T + key] : 0;
+    dew0 = __builtin_amdgcn_readfirstlane(de);
+    dew1 = __builtin_amdgcn_readlane(de, 31);
+    dw.edge = dew1;
+    dw.bits = (uint32_t)__builtin_amdgcn_ballot_w64(de == key + 1);  // lanes l and l + 32 hold the same key
+  }
   const float c = scale * LOG2E;
   const bf16_t* Kb = K + (int64_t)b * T * ld + (int64_t)kvh * HD;
   const bf16_t* Vb = V + (int64_t)b * T * ld + (int64_t)kvh * HD;
@@ -1318,9 +1460,11 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
   // per-lane DMA source offsets (constant over tiles): physical chunk p of row r carries logical
   // chunk p ^ key(r) of the soff<HD> swizzle (an XOR involution)
   const int wu = __builtin_amdgcn_readfirstlane(w);
-  uint32_t vq[IPW], vd[IPW];
+  // DOC: one offset per operand, the row step of a wave's pieces in the scalar base (see TileDma)
+  static_assert(!DOC || (NW * RPI) % 16 == 0, "pieces of one wave must share the swizzle phase");
+  uint32_t vq[DOC ? 1 : IPW], vd[DOC ? 1 : IPW];
 #pragma unroll
-  for (int i = 0; i < IPW; ++i) {
+  for (int i = 0; i < (DOC ? 1 : IPW); ++i) {
     const int row = (wu + NW * i) * RPI + lane / CPR, p = lane % CPR;
     const int lch = (soff<HD>(row, p * 8) - row * HD) / 8;  // soff maps logical -> physical; XOR: same map back
     vq[i] = (uint32_t)(((int64_t)row * ld + lch * 8) * 2);
@@ -1329,7 +1473,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
   const uint32_t qs_a = lds_addr(Qs), do_a = lds_addr(dOs), ls_a = lds_addr(lse_s), ds_a = lds_addr(del_s);
 
   const int qstart = (kb * KB) / BQ * BQ;
-  const int ntq = (T - qstart + BQ - 1) / BQ;
+  // DOC: no query at or past the end of the block's last key's document sees any of its keys (clamped to
+  // (qstart, T]: bounds that break the t < doc_end[t] <= T invariant must not move the loads out of the sequence)
+  int qend = T;
+  if constexpr (DOC)
+    qend = min(max(__builtin_amdgcn_readfirstlane(KS[(int64_t)b * T + min(kb * KB + KB, T) - 1]), qstart + 1), T);
+  const int ntq = (qend - qstart + BQ - 1) / BQ;
   const int nit = ntq * rep;
   // order bit 1: walk the query tiles from the LAST one down to the diagonal.  Every key block of a head
   // ends at query tile ntq - 1, so descending walks line the key blocks up on the SAME Q / dO tile at the
@@ -1352,8 +1501,13 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
       const uint32_t off = (uint32_t)(buf * BQ * HD * 2 + (wu + NW * i) * 1024);
-      if (part & 1) gdma(sq, vq[i], qs_a + off);
-      if (part & 2) gdma(sd, vd[i], do_a + off);
+      if constexpr (DOC) {
+        if (part & 1) gdma(sq + (int64_t)(i * NW * RPI) * ld, vq[0], qs_a + off);
+        if (part & 2) gdma(sd + (int64_t)(i * NW * RPI) * ldo, vd[0], do_a + off);
+      } else {
+        if (part & 1) gdma(sq, vq[i], qs_a + off);
+        if (part & 2) gdma(sd, vd[i], do_a + off);
+      }
     }
     ND_STAMP(stp.mark(9);)
     if ((part & 4) && wu < BQ / 64) {  // one 64-float wave-instruction per 64 rows
@@ -1400,6 +1554,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
         if (qs < 3 && it + 1 < nit) issue(it + 1, 1 << qs);  // before the skip test: every wave issues its pieces
       const int qsub = q0 + qs * 32;
       if (kw0 > qsub + 31 || kw0 >= T) continue;  // wave-uniform: no query >= any of our keys
+      if (DOC && qsub >= dew1) continue;          // wave-uniform: every query past our last key's document
       // All LDS fragments of this step are issued up front (row reads for S / dP, transposing reads
       // for dV / dK) so their latency hides behind the MFMA chains and the softmax VALU instead of
       // being exposed one s_waitcnt at a time.
@@ -1453,7 +1608,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
       xprio<1>(0);
       ND_STAMP(stp.mark(3);)
       xprio<16>(1);
-      const bool diag = (kw0 + 31 > qsub) || (qsub + 31 >= T) || (key >= T) || (PAD && kw0 < ks);
+      const bool diag = (kw0 + 31 > qsub) || (qsub + 31 >= T) || (key >= T) || (PAD && kw0 < ks) || (DOC && qsub + 31 >= dew0);
       if constexpr ((ABL & 4) != 0) {
       } else if (!diag) {
         if constexpr ((ND_ATTN_X & 2) != 0) {
@@ -1476,6 +1631,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
           s[r] = p;
           dp[r] = p * dp[r];
         }
+        }
+      } else if constexpr (DOC) {
+        // key <= qq < doc_end (every query of a tile and every key of a running wave is < T)
+        const uint32_t vis = bit_range(key - qsub, dw.end_of(kw0, c32) - qsub) >> (4 * h);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = (vis & (1u << ((r & 3) + 8 * (r >> 2)))) ? fexp2(s[r] * c) : 0.f;
+          s[r] = p;
+          dp[r] = p * dp[r];
         }
       } else {
 #pragma unroll
@@ -1681,4 +1845,50 @@ ND_API int nd_attn_bwd_fused(const void* q, const void* k, const void* v, const 
                              int rope_mode, hipStream_t s) {
   return nd_attn_bwd_fused_ks(q, k, v, o, dout, lse, dq, dk, dv, ws, B, nh, nkv, T, hd, ld, ldo, cosT, sinT, scale,
                               rope_mode, nullptr, s);
+}
+
+// Document-masked fused backward (see nd_attn_fwd_doc): dQ walks the key tiles from its block's first document
+// (doc_start), dK/dV walks the query tiles up to the end of its block's last document (doc_end).  Default block
+// shapes only; no atomics, bitwise reproducible like the other modes.
+template <int HD, bool ROPE_OUT>
+static int bwd_fused_doc_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, void* dq, void* dk, void* dv, float* ws, int B, int nh, int nkv,
+                                int T, int64_t ld, int64_t ldo, const float* cosT, const float* sinT, float scale,
+                                const int* doc_start, const int* doc_end, hipStream_t s) {
+  const int nb = (T + 127) / 128;
+  const int64_t n = (int64_t)B * nh * T;
+  float *nl = ws, *nd = ws + n;
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, false, ROPE_OUT, true, true, MASK_DOC>), dim3(nb * B * nh), dim3(256), 0, s,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse, nullptr,
+                     (bf16_t*)dq, B, nh, nkv, T, ld, ldo, scale, cosT, sinT, (const bf16_t*)o, nl, nd, doc_start,
+                     attn_order());
+  if (T % 128 == 0)
+    hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<HD, ROPE_OUT, 128, MASK_DOC>), dim3(nb * B * nkv), dim3(256), 0, s,
+                       (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, nl, nd, (bf16_t*)dk,
+                       (bf16_t*)dv, B, nh, nkv, T, ld, ldo, scale, cosT, sinT, doc_end, dkdv_order(nh, nkv));
+  else
+    hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<HD, ROPE_OUT, 64, MASK_DOC>), dim3(nb * B * nkv), dim3(256), 0, s,
+                       (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, nl, nd, (bf16_t*)dk,
+                       (bf16_t*)dv, B, nh, nkv, T, ld, ldo, scale, cosT, sinT, doc_end, dkdv_order(nh, nkv));
+  ND_LAUNCH_CHECK();
+}
+
+ND_API int nd_attn_bwd_fused_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                 const float* lse, void* dq, void* dk, void* dv, float* ws, int B, int nh, int nkv,
+                                 int T, int hd, int64_t ld, int64_t ldo, const float* cosT, const float* sinT,
+                                 float scale, int rope_mode, const int* doc_start, const int* doc_end, hipStream_t s) {
+  if (nh % nkv || (ld % 8) || (ldo % 8) || T % 64 || ws == nullptr || !doc_start || !doc_end)
+    return (int)hipErrorInvalidValue;
+  if ((rope_mode != 0 && rope_mode != 2) || (rope_mode == 2 && !(cosT && sinT))) return (int)hipErrorInvalidValue;
+  switch (hd) {
+#define ND_BD(H)                                                                                                     \
+  case H:                                                                                                            \
+    return (rope_mode == 2 ? bwd_fused_doc_launch<H, true> : bwd_fused_doc_launch<H, false>)(                        \
+        q, k, v, o, dout, lse, dq, dk, dv, ws, B, nh, nkv, T, ld, ldo, cosT, sinT, scale, doc_start, doc_end, s);
+    ND_BD(32)
+    ND_BD(64)
+    ND_BD(128)
+#undef ND_BD
+    default: return (int)hipErrorInvalidValue;
+  }
 }

@@ -50,7 +50,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv: Optional[List[str]] = None) -> TrainArgs:
-    ns = build_parser().parse_args(argv)
+    parser = build_parser()
+    ns = parser.parse_args(argv)
+    if ns.doc_mask and ns.data == "hf":
+        parser.error("--doc-mask is for packed data (--data memmap | synthetic), not --data hf")
     return TrainArgs(**vars(ns))
 
 

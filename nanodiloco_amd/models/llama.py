@@ -71,8 +71,11 @@ class _GradHook(torch.autograd.Function):
 class LlamaForCausalLM:
     def __init__(self, config: LlamaConfig, device="cpu", compute_dtype: torch.dtype = torch.float32,
                  store: Optional[ParamStore] = None, activation_checkpointing: bool = False, fp8: bool = False,
-                 fp8_wgrad: bool = False, residual_dtype: Optional[torch.dtype] = None):
+                 fp8_wgrad: bool = False, residual_dtype: Optional[torch.dtype] = None, doc_mask: bool = False):
         self.config = config
+        # packed windows: attention stays inside each EOS-separated document (ops.doc_bounds)
+        self.doc_mask = bool(doc_mask)
+        self.debug_checks = False  # validate the derived bounds every forward (host sync: never under graph capture)
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype
         # residual stream: fp32 (default, the autocast recipe) or bf16 (Megatron's default; ops/norm.py)
@@ -200,7 +203,7 @@ class LlamaForCausalLM:
             return None
         return self.fp8.dy_target(key) if grad else self.fp8.x_target(key)
 
-    def _layer(self, i, h, y, cos, sin, B, T, next_norm, y8=None, kstart=None):
+    def _layer(self, i, h, y, cos, sin, B, T, next_norm, y8=None, kstart=None, doc=None):
         c = self.config
         p = f"model.layers.{i}."
         cdt = self.compute_dtype
@@ -227,7 +230,7 @@ class LlamaForCausalLM:
             qkv = self._linear(f"{i}.qkv", y, w_qkv, self._fused(qn, "grad"), y8)
             rotated = False
         o = ops.attention(qkv, cos, sin, B, T, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
-                          inplace=True, kstart=kstart, rotated=rotated)
+                          inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc)
         a = self._linear(f"{i}.o", o, self._w(p + "self_attn.o_proj.weight"), self._g(p + "self_attn.o_proj.weight"))
         q_gu = self._q8(f"{i}.gu")
         y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"),
@@ -261,9 +264,15 @@ class LlamaForCausalLM:
 
     def hidden_states(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Final-normed hidden states [B*T, d] in the compute dtype.  ``attention_mask`` (HF [B, T],
-        left or right padded) becomes a per-sequence key start for the attention kernels."""
+        left or right padded) becomes a per-sequence key start for the attention kernels.  With ``doc_mask`` the
+        document bounds of the packed window are derived from ``input_ids`` once and shared by every layer."""
         c = self.config
+        if self.doc_mask and attention_mask is not None:
+            raise ValueError("doc_mask (packed documents) and attention_mask (padded batches) cannot be combined")
         kstart = ops.key_start(attention_mask) if attention_mask is not None else None
+        doc = ops.doc_bounds(input_ids, c.eos_token_id) if self.doc_mask else None
+        if doc is not None and self.debug_checks:
+            ops.check_doc_bounds(*doc)
         B, T = input_ids.shape
         cdt = self.compute_dtype
         eps = c.rms_norm_eps
@@ -286,9 +295,9 @@ class LlamaForCausalLM:
             nxt = f"model.layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "model.norm.weight"
             if self.activation_checkpointing and self.training and torch.is_grad_enabled():
                 from torch.utils.checkpoint import checkpoint
-                m, h = checkpoint(self._layer, i, h, y, cos, sin, B, T, nxt, None, kstart, use_reentrant=False)
+                m, h = checkpoint(self._layer, i, h, y, cos, sin, B, T, nxt, None, kstart, doc, use_reentrant=False)
             else:
-                m, h = self._layer(i, h, y, cos, sin, B, T, nxt, y8, kstart)
+                m, h = self._layer(i, h, y, cos, sin, B, T, nxt, y8, kstart, doc)
             if hook is not None and i + 1 < L:
                 # layer i+1's gradients are final once the backward of the add+norm that produces its
                 # input (and owns its input_layernorm weight) has run: hook that norm's input

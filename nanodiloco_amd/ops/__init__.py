@@ -8,7 +8,8 @@ from .linear import linear, wgrad_accumulate, set_wgrad_overlap, wgrad_overlap_e
 from .norm import rmsnorm, rmsnorm_res, add_rmsnorm
 from .embedding import embedding
 from .swiglu import swiglu
-from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding
+from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding, doc_bounds, \
+    check_doc_bounds
 from .cross_entropy import lm_head_ce, IGNORE_INDEX
 from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov
 from .qcomm import pseudograd_q, qreduce, outer_nesterov_q
@@ -18,6 +19,7 @@ from . import reference
 __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "linear", "wgrad_accumulate",
            "set_wgrad_overlap", "wgrad_overlap_enabled", "join_wgrad", "set_wgrad_group", "wgrad_group_enabled",
            "set_dgrad_transposed", "dgrad_transposed_enabled", "transpose_into",
-           "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "lm_head_ce",
+           "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
+           "lm_head_ce",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
            "outer_nesterov_q", "reference"]

@@ -144,6 +144,9 @@ def _declare(L: ctypes.CDLL):
         "nd_attn_fwd_ks": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P, P],
         "nd_attn_bwd_ks": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, P],
         "nd_attn_bwd_fused_ks": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, P],
+        # document-masked (packed windows): the _ks signatures with (doc_start, doc_end) in place of ks
+        "nd_attn_fwd_doc": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P, P, P],
+        "nd_attn_bwd_fused_doc": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, P, P],
         "nd_attn_bwd_pre": [P, P, P, I, I, I, L64, L64, P],
         "nd_attn_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
         "nd_attn_bwd_fused": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],

@@ -123,15 +123,28 @@ def padded_causal_mask(kstart: torch.Tensor, T: int) -> torch.Tensor:
     return (causal[None] & real_k).unsqueeze(1)
 
 
+def doc_causal_mask(doc_start: torch.Tensor, T: int) -> torch.Tensor:
+    """Boolean [B, 1, T, T] (True = attend): causal & key is inside the query's document of a packed window,
+    ``doc_start[b, q] <= k <= q`` (``ops.attention.doc_bounds``).  Every query sees itself: no empty row."""
+    t = torch.arange(T, device=doc_start.device)
+    causal = t[None, :] <= t[:, None]
+    same_doc = t.view(1, 1, T) >= doc_start.view(-1, T, 1).to(t.dtype)
+    return (causal[None] & same_doc).unsqueeze(1)
+
+
 def attention_block(qkv: torch.Tensor, cos, sin, B: int, T: int, nh: int, nkv: int, hd: int,
-                    use_sdpa: bool = True, kstart: torch.Tensor = None) -> torch.Tensor:
+                    use_sdpa: bool = True, kstart: torch.Tensor = None, doc_bounds=None) -> torch.Tensor:
     """qkv [B*T, (nh+2nkv)*hd] -> RoPE -> causal attention -> [B*T, nh*hd] (autograd-capable).
-    ``kstart``: left-padding key start per sequence (see ``ops.attention.key_start``)."""
+    ``kstart``: left-padding key start per sequence (see ``ops.attention.key_start``).
+    ``doc_bounds``: (doc_start, doc_end) of a packed window (see ``ops.attention.doc_bounds``)."""
     q, k, v = split_qkv(qkv, B, T, nh, nkv, hd)
     q = apply_rope(q, cos[:T], sin[:T])
     k = apply_rope(k, cos[:T], sin[:T])
-    if kstart is not None:
-        mask = padded_causal_mask(kstart.to(qkv.device), T)
+    if kstart is not None and doc_bounds is not None:
+        raise ValueError("kstart (left padding) and doc_bounds (packed documents) cannot be combined")
+    if kstart is not None or doc_bounds is not None:
+        mask = padded_causal_mask(kstart.to(qkv.device), T) if kstart is not None \
+            else doc_causal_mask(doc_bounds[0].to(qkv.device), T)
         if nkv != nh:
             k = k.repeat_interleave(nh // nkv, dim=1)
             v = v.repeat_interleave(nh // nkv, dim=1)

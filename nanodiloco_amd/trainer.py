@@ -94,6 +94,8 @@ class TrainArgs:
     tokenizer: str = "huggyllama/llama-7b"
     debug_checks: bool = False
     mask_pad_labels: bool = True
+    doc_mask: bool = False         # packed data (memmap / synthetic): attention stays inside each EOS-separated
+                                   # document of a window (block-diagonal causal; ops.doc_bounds, docs/DESIGN.md)
     deterministic: bool = False    # bitwise-reproducible step: no float atomics (ops/determinism.py)
     skip_nonfinite: bool = False   # device-side skip of inner steps whose grad norm is NaN/Inf (no host sync)
     collective_timeout_s: float = 1800.0
@@ -157,6 +159,18 @@ def auto_micro_batch(cfg: LlamaConfig, seq_len: int, batch_size: int, device: to
     return mb
 
 
+def check_doc_mask(doc_mask: bool, data_kind: str, seq_length: int, on_gpu: bool, ops_backend: str = "auto") -> None:
+    """``--doc-mask`` is for packed windows: the HF path pads and masks its batches already, and the attention
+    kernels' document mode needs whole 64-key tiles."""
+    if not doc_mask:
+        return
+    if data_kind == "hf":
+        raise ValueError("--doc-mask is for packed data (--data memmap | synthetic); --data hf batches are padded "
+                         "and masked by their attention_mask already")
+    if on_gpu and ops_backend != "torch" and seq_length % 64:
+        raise ValueError(f"--doc-mask on a GPU needs --seq-length to be a multiple of 64 (got {seq_length})")
+
+
 def _resolve_data_kind(a: TrainArgs) -> str:
     if a.data != "auto":
         return a.data
@@ -198,10 +212,13 @@ class Trainer:
         if a.fp8 or a.dtype == "fp8":
             from .ops.fp8 import set_fp8_keep_fused
             set_fp8_keep_fused(a.fp8_keep_fused)
+        self.data_kind = _resolve_data_kind(a)
+        check_doc_mask(a.doc_mask, self.data_kind, a.seq_length, e.device.type == "cuda", a.ops)
         self.model = LlamaForCausalLM(self.llama_config, e.device, self.compute_dtype,
                                       activation_checkpointing=a.activation_checkpointing,
                                       fp8=a.fp8 or a.dtype == "fp8", fp8_wgrad=a.fp8_wgrad,
-                                      residual_dtype=_residual_dtype(a.residual_dtype, a.fp8 or a.dtype == "fp8")).init_weights(a.seed)
+                                      residual_dtype=_residual_dtype(a.residual_dtype, a.fp8 or a.dtype == "fp8"),
+                                      doc_mask=a.doc_mask).init_weights(a.seed)
         inner = FlatAdamW(self.model.store, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm,
                           skip_nonfinite=a.skip_nonfinite)
         outer = FlatOuterNesterov(self.model.store, lr=a.outer_lr, momentum=a.outer_momentum)
@@ -211,7 +228,6 @@ class Trainer:
                              debug_checks=a.debug_checks)
         self.inner_sync = InnerGradSync(self.model, self.diloco.inner_comm)
         self.loss_scale = (1.0 if a.legacy_grad_sum else 1.0 / self.grad_accum) / e.inner_dp
-        self.data_kind = _resolve_data_kind(a)
         self.data = build_data(self.data_kind, vocab_size=self.llama_config.vocab_size, seq_len=a.seq_length,
                                batch_size=a.per_device_batch_size, seed=a.seed, rank=e.rank, world_size=e.world_size,
                                device=e.device, dataset_path=a.dataset_path, tokenizer=a.tokenizer,
@@ -262,6 +278,7 @@ class Trainer:
                 raise ValueError("--hip-graph needs a GPU, --inner-dp 1, no --fp8 and no --force-collectives")
             from .utils.graphs import GraphedMicroStep
             self.graphed = GraphedMicroStep(self.model)
+        self.model.debug_checks = bool(a.debug_checks) and self.graphed is None
         self.run_name = create_run_name("nanodiloco", self.run_config, is_debug=False)
         self.timer = PhaseTimer(a.phase_timing)
         self.sink = make_sink(e.rank, a.project, self.run_name, {**self.run_config, **dataclasses.asdict(a)},
