@@ -38,9 +38,9 @@ template <int SDT>
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, void* __restrict__ sh,
                                                     int64_t n, const float* __restrict__ part, int nparts, float lr,
-                                                    float b1, float b2, float eps, float wd, float bc1, float bc2,
-                                                    float max_norm, float* __restrict__ norm_out, int skip_nonfinite,
-                                                    int* __restrict__ skipped) {
+                                                    float omb1, float b2, float omb2, float eps, float wd, float bc1,
+                                                    float bc2, float max_norm, float* __restrict__ norm_out,
+                                                    int skip_nonfinite, int* __restrict__ skipped) {
   __shared__ float red[4];
   float coef = 1.f;
   if (part) {
@@ -60,7 +60,6 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
   const float decay = 1.f - lr * wd;
   const float step = lr / bc1;
   const float rbc2 = 1.f / sqrtf(bc2);
-  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
   auto upd = [&](float& pp, float gg, float& mm, float& vv) {
     gg *= coef;
     pp *= decay;
@@ -93,16 +92,19 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// b1 / b2 arrive as doubles: 1 - beta is formed before the rounding to fp32 (1.f - 0.999f is 0.99998713e-3,
+// which scaled every second moment by 1 - 1.3e-5 against torch.optim.AdamW's 1 - beta2)
 ND_API int nd_adamw_step(float* p, const float* g, float* m, float* v, void* sh, int shdt, int64_t n,
-                         const float* part, int nparts, float lr, float b1, float b2, float eps, float wd, float bc1,
+                         const float* part, int nparts, float lr, double b1, double b2, float eps, float wd, float bc1,
                          float bc2, float max_norm, float* norm_out, int skip_nonfinite, int* skipped, hipStream_t s) {
   const unsigned grid = stream_grid(n >> 2);
+  const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), b2f = (float)b2;
   if (sh && shdt == BF16)
-    hipLaunchKernelGGL(adamw_kernel<BF16>, dim3(grid), dim3(256), 0, s, p, g, m, v, sh, n, part, nparts, lr, b1, b2, eps,
-                       wd, bc1, bc2, max_norm, norm_out, skip_nonfinite, skipped);
+    hipLaunchKernelGGL(adamw_kernel<BF16>, dim3(grid), dim3(256), 0, s, p, g, m, v, sh, n, part, nparts, lr, omb1, b2f,
+                       omb2, eps, wd, bc1, bc2, max_norm, norm_out, skip_nonfinite, skipped);
   else
-    hipLaunchKernelGGL(adamw_kernel<F32>, dim3(grid), dim3(256), 0, s, p, g, m, v, nullptr, n, part, nparts, lr, b1, b2,
-                       eps, wd, bc1, bc2, max_norm, norm_out, skip_nonfinite, skipped);
+    hipLaunchKernelGGL(adamw_kernel<F32>, dim3(grid), dim3(256), 0, s, p, g, m, v, nullptr, n, part, nparts, lr, omb1, b2f,
+                       omb2, eps, wd, bc1, bc2, max_norm, norm_out, skip_nonfinite, skipped);
   ND_LAUNCH_CHECK();
 }
 

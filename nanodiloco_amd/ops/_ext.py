@@ -127,7 +127,7 @@ def dtcode(t: torch.Tensor) -> int:
 
 def _declare(L: ctypes.CDLL):
     """Argument types for every exported launcher (all return hipError_t as int)."""
-    P, I, F, L64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
+    P, I, F, L64, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_double
     sigs = {
         "nd_version": [],
         # norms
@@ -164,7 +164,7 @@ def _declare(L: ctypes.CDLL):
         "nd_embedding_bwd_sorted": [P, P, P, I, P, P, L64, I, I, P],
         # optimizer / outer step (flat buffers)
         "nd_sumsq_partial": [P, L64, P, I, P],
-        "nd_adamw_step": [P, P, P, P, P, I, L64, P, I, F, F, F, F, F, F, F, F, P, I, P, P],
+        "nd_adamw_step": [P, P, P, P, P, I, L64, P, I, F, D, D, F, F, F, F, F, P, I, P, P],
         "nd_pseudograd": [P, P, P, I, L64, P],
         "nd_outer_nesterov": [P, P, P, I, P, P, I, L64, F, F, F, I, P, P, P],
         "nd_axpby": [P, P, L64, F, F, P],

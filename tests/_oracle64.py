@@ -1,0 +1,232 @@
+"""float64 oracles of the row-wise and streaming ops, one per-element error rule, spiked test inputs.
+
+Every function here is plain PyTorch in float64, written from the math in the kernel headers
+(``csrc/norm.hip``, ``rope.hip``, ``swiglu.hip``, ``cross_entropy.hip``, ``embedding.hip``, ``optim.hip``,
+``transpose.hip``) and ``ops/reference.py``; none of them calls the code under test.  They run on whatever
+device their inputs live on; ``tests/test_oracle64_cpu.py`` checks each against the project's torch twin
+on the CPU, ``tests/test_rowwise_edges_gpu.py`` uses them against the HIP kernels.
+
+The error rule (``check``), per element:
+  output stored as bf16:  |out - ref64| <= 2^-8 * |ref64| + slack     (2^-8: half a bf16 ulp, relative)
+  output stored as fp32:  |out - ref64| <= slack
+  slack = margin * max|twin32 - ref64| over the same tensor, twin32 = the fp32 PyTorch twin on the same
+  inputs (measured against the oracle, never against the kernel); margin 8 unless docs/PARITY.md says why not.
+"""
+import math
+
+import torch
+
+BF16_HALF_ULP = 2.0 ** -8
+MARGIN = 8.0
+
+
+# ------------------------------------------------------------------------------------------ error rule
+def excess_ratio(out, ref64, twin32, rel=None):
+    """max over elements of (|out - ref64| - rel * |ref64|) / max|twin32 - ref64|: the margin this output
+    needs (<= 0: inside the bf16 rounding term alone).  inf when the twin is exact and the output is not."""
+    ref64 = ref64.double()
+    if rel is None:
+        rel = BF16_HALF_ULP if out.dtype == torch.bfloat16 else 0.0
+    err = (out.double() - ref64).abs() - rel * ref64.abs()
+    unit = (twin32.double() - ref64).abs().max().item() if ref64.numel() else 0.0
+    worst = err.max().item() if ref64.numel() else 0.0
+    if worst != worst:
+        return float("nan")
+    if worst <= 0.0:
+        return 0.0
+    return worst / unit if unit > 0 else float("inf")
+
+
+def check(out, ref64, twin32, margin=MARGIN, name="", rel=None, report=None, note=""):
+    """Assert the error rule on EVERY element of ``out``; on failure name the worst element.  ``report``
+    (a dict) collects the measured margin per name (max over calls) for the table in docs/PARITY.md."""
+    assert out.shape == ref64.shape == twin32.shape, (name, out.shape, ref64.shape, twin32.shape)
+    ref64 = ref64.double()
+    if rel is None:
+        rel = BF16_HALF_ULP if out.dtype == torch.bfloat16 else 0.0
+    if ref64.numel() == 0:
+        return
+    unit = (twin32.double() - ref64).abs().max().item()
+    slack = margin * unit
+    err = (out.double() - ref64).abs()
+    bound = rel * ref64.abs() + slack
+    over = err - bound
+    ratio = excess_ratio(out, ref64, twin32, rel)
+    if report is not None:
+        prev = report.get(name, 0.0)
+        report[name] = ratio if (ratio != ratio or ratio > prev) else prev
+    bad = ~(err <= bound)  # NaN counts as bad
+    if bool(bad.any()):
+        flat = torch.where(bad.reshape(-1), over.reshape(-1).nan_to_num(float("inf")),
+                           torch.full_like(over.reshape(-1), float("-inf"))).argmax().item()
+        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), ref64.shape)) if ref64.dim() else ()
+        raise AssertionError(
+            f"{name}{' [' + note + ']' if note else ''}: {int(bad.sum())} of {ref64.numel()} elements outside the "
+            f"rule; worst at {idx}: "
+            f"out={out.reshape(-1)[flat].item()!r} ref64={ref64.reshape(-1)[flat].item()!r} "
+            f"err={err.reshape(-1)[flat].item():.3e} bound={bound.reshape(-1)[flat].item():.3e} "
+            f"twin32={twin32.reshape(-1)[flat].item()!r} "
+            f"(slack {slack:.3e} = {margin} x twin32 error {unit:.3e}; needs margin {ratio:.3g})")
+
+
+# ------------------------------------------------------------------------------------------ inputs
+def spike_columns(cols):
+    """Column order of the spikes: the last 8 columns, the first column of every 512-column chunk, then every
+    other position -- so even a few rows hit the places where a dropped or mis-indexed chunk shows."""
+    first = list(range(max(0, cols - 8), cols)) + [c for c in range(0, cols, 512)]
+    seen, order = set(), []
+    for c in first + list(range(cols)):
+        if c not in seen:
+            seen.add(c)
+            order.append(c)
+    return order
+
+
+def spiked(rows, cols, device, scale=1.0, start=0):
+    """randn * scale with one +-8*scale spike per row at a column that walks through ``spike_columns``."""
+    x = torch.randn(rows, cols, device=device) * scale
+    order = torch.tensor(spike_columns(cols), device=device)
+    r = torch.arange(rows, device=device)
+    col = order[(r + start) % order.numel()]
+    sign = 1.0 - 2.0 * ((r // 2) % 2).to(x.dtype)
+    x[r, col] = 8.0 * scale * sign
+    return x
+
+
+# ------------------------------------------------------------------------------------------ RMSNorm
+def f32_scalar(v):
+    """The value a C ``float`` argument takes."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def rmsnorm(h, w, eps, a=None, round_hnew=False, dy=None, dres=None):
+    """h_new = h (+ a); rstd = 1/sqrt(mean(h_new^2) + eps); y = w * h_new * rstd.
+    ``round_hnew``: h_new is rounded to bf16 (after the fp32 sum, as stored) before the statistics.
+    With ``dy``: g = dy * w, dx = rstd * (g - xhat * mean(g * xhat)) + dres, da = dx, dw = sum_rows dy * xhat.
+    Returns a dict of float64 tensors y, h_new, rstd and (with dy) dx, da, dw."""
+    hn = h.double()
+    if a is not None:
+        hn = hn + a.double()
+    if round_hnew:
+        hn = hn.float().bfloat16().double()
+    rstd = 1.0 / torch.sqrt((hn * hn).mean(-1, keepdim=True) + f32_scalar(eps))
+    xhat = hn * rstd
+    out = {"y": w.double() * xhat, "h_new": hn, "rstd": rstd[..., 0]}
+    if dy is not None:
+        d = dy.double()
+        g = d * w.double()
+        dx = rstd * (g - xhat * (g * xhat).mean(-1, keepdim=True))
+        if dres is not None:
+            dx = dx + dres.double()
+        out.update(dx=dx, da=dx, dw=(d * xhat).reshape(-1, hn.shape[-1]).sum(0))
+    return out
+
+
+def colsum_add(part, out):
+    return out.double() + part.double().sum(0)
+
+
+# ------------------------------------------------------------------------------------------ RoPE
+def rope(qkv, cos, sin, B, T, nh, nkv, hd, inverse=False):
+    """Half-split rotation of the q and k heads of packed rows [B*T, (nh + 2 nkv) * hd]; element i pairs with
+    i + hd/2; the fp32 tables [T, hd] are taken as given (first half read) and widened; v passes through."""
+    x = qkv.double()
+    nrot, half = nh + nkv, hd // 2
+    blk = x[:, :nrot * hd].reshape(B, T, nrot, hd)
+    c = cos[:T, :half].double()[None, :, None, :]
+    s = sin[:T, :half].double()[None, :, None, :]
+    if inverse:
+        s = -s
+    x1, x2 = blk[..., :half], blk[..., half:]
+    rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).reshape(B * T, nrot * hd)
+    return torch.cat([rot, x[:, nrot * hd:]], dim=1)
+
+
+# ------------------------------------------------------------------------------------------ SwiGLU
+def swiglu_fwd(gu):
+    g, u = gu.double().chunk(2, dim=-1)
+    return g * torch.sigmoid(g) * u
+
+
+def swiglu_bwd(dy, gu):
+    """dg = dy * u * s * (1 + g * (1 - s)), du = dy * g * s, s = sigmoid(g); returns d(gate|up)."""
+    g, u = gu.double().chunk(2, dim=-1)
+    d = dy.double()
+    s = torch.sigmoid(g)
+    return torch.cat([d * u * s * (1.0 + g * (1.0 - s)), d * g * s], dim=-1)
+
+
+# ------------------------------------------------------------------------------------------ embedding
+def _masked_ids(ids, V):
+    ids = ids.reshape(-1)
+    ok = (ids >= 0) & (ids < V)
+    return torch.where(ok, ids, torch.zeros_like(ids)), ok  # never index with a bad id
+
+
+def embedding_fwd(ids, W):
+    safe, ok = _masked_ids(ids, W.shape[0])
+    return W.double().index_select(0, safe) * ok[:, None].double()
+
+
+def embedding_bwd(ids, dy, V, base=None):
+    """gW[id] += dy[row] over the in-range ids (out-of-range rows contribute nothing)."""
+    safe, ok = _masked_ids(ids, V)
+    d = dy.double() * ok[:, None].double()
+    gw = (base.double().clone() if base is not None
+          else torch.zeros(V, dy.shape[1], dtype=torch.float64, device=dy.device))
+    return gw.index_add_(0, safe, d)
+
+
+# ------------------------------------------------------------------------------------------ cross-entropy
+def ce_rows(logits, targets, scale, ignore_index=-100):
+    """Per row: lse, loss = lse - x[target], dlogits = (softmax - onehot) * scale; ignored rows give 0 loss and
+    0 gradient.  Returns (lse, row_loss, dlogits) in float64."""
+    x = logits.double()
+    lse = torch.logsumexp(x, dim=-1)
+    ok = targets != ignore_index
+    safe = torch.where(ok, targets, torch.zeros_like(targets))
+    picked = x.gather(1, safe[:, None])[:, 0]
+    loss = torch.where(ok, lse - picked, torch.zeros_like(lse))
+    p = torch.exp(x - lse[:, None])
+    p.scatter_add_(1, safe[:, None], -torch.ones_like(p[:, :1]))
+    return lse, loss, p * (ok[:, None].double() * float(scale))
+
+
+# ------------------------------------------------------------------------------------------ optimizer
+def adamw(master, grad, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_norm=1.0):
+    """Clip by global norm (coef = min(1, max_norm / (norm + 1e-6))), decoupled decay, lerp first moment,
+    second moment, bias-corrected step.  Returns (master, m, v, norm), all float64, inputs untouched."""
+    b1, b2 = betas
+    p, g, m, v = master.double(), grad.double(), m.double(), v.double()
+    norm = g.norm()
+    if max_norm is not None:
+        g = g * torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+    p = p * (1.0 - lr * weight_decay)
+    m = m + (g - m) * (1.0 - b1)
+    v = v * b2 + (1.0 - b2) * g * g
+    denom = v.sqrt() / math.sqrt(1.0 - b2 ** step) + eps
+    p = p - (lr / (1.0 - b1 ** step)) * (m / denom)
+    return p, m, v, norm
+
+
+def pseudograd(sync, local):
+    return sync.double() - local.double()
+
+
+def outer_nesterov(master, sync, delta_sum, mom, inv_world, lr, momentum, first, drift_base=None):
+    """d = delta_sum * inv_world; mom = d (first) or momentum * mom + d; new = sync - lr * (d + momentum * mom);
+    master = new, or with drift_base: new + (master - (sync - drift_base)); sync = new.
+    Returns (master, sync, mom) in float64."""
+    d = delta_sum.double() * inv_world
+    mom = d.clone() if first else mom.double() * momentum + d
+    new = sync.double() - lr * (d + momentum * mom)
+    if drift_base is not None:
+        master = master.double() + drift_base.double() - sync.double() + new
+    else:
+        master = new.clone()
+    return master, new, mom
+
+
+# ------------------------------------------------------------------------------------------ transpose
+def transpose(x):
+    return x.double().t()

@@ -239,8 +239,13 @@ def test_ce_fused_fp8_refuses_other_shapes():
 @pytest.mark.parametrize("residual", [False, True])
 def test_fused_rmsnorm_quant_bitwise(residual, hdt):
     """RMSNorm fwd (y -> e4m3) and bwd (branch grad -> e5m2) fp8 side outputs == separate casts (fp32 and bf16
-    residual streams)."""
-    rows, cols = 777, 1024
+    residual streams); 520 columns (a chunk with one active lane) and 4096 (the backward's 64 KiB of dynamic LDS
+    next to the fused variants' 16 B of static LDS) beside 1024."""
+    for cols in (1024, 520, 4096):
+        _fused_rmsnorm_quant_bitwise(residual, hdt, 777, cols)
+
+
+def _fused_rmsnorm_quant_bitwise(residual, hdt, rows, cols):
     h = torch.randn(rows, cols, device="cuda").to(hdt)
     a = torch.randn(rows, cols, device="cuda").bfloat16()
     w = 1 + 0.1 * torch.randn(cols, device="cuda")
