@@ -1,6 +1,6 @@
 // The outer SGD-Nesterov update of one element, shared by the fp32 / bf16 transport (optim.hip
-// outer_kernel) and the block-quantised transport (qcomm.hip outer_q_kernel): ONE definition, so the two
-// cannot drift apart.
+// outer_kernel), the block-quantised transport (qcomm.hip outer_q_kernel) and the Streaming DiLoCo fragment
+// update (stream_outer.hip frag_outer_mix_kernel): ONE definition, so they cannot drift apart.
 //   d = delta_sum * inv_world (formed by the caller)
 //   buf = first ? d : mu*buf + d ;  theta = sync - lr*(d + mu*buf) ;  sync = theta
 //   has_drift: p = theta + (p - (sync_old - drift)) (overlapped mode) ; else p = theta.  Returns the new p.
@@ -19,6 +19,13 @@ __device__ __forceinline__ float outer_update(float d, float& b, float& so, floa
   const float np = has_drift ? th + (pv - (so - drift)) : th;
   so = th;
   return np;
+}
+
+// Streaming DiLoCo merge of the new outer weights th into the local weights p that kept drifting while the
+// fragment's all-reduce was in flight: (1 - alpha) * th + alpha * p, as ONE fused rounding.  alpha == 0 (the
+// local progress is dropped, p is not needed) returns th itself, so that case is bitwise outer_update's.
+__device__ __forceinline__ float outer_mix(float th, float p, float alpha) {
+  return alpha == 0.f ? th : __fmaf_rn(alpha, p - th, th);
 }
 
 }  // namespace nd

@@ -11,7 +11,8 @@ from .swiglu import swiglu
 from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding, doc_bounds, \
     check_doc_bounds
 from .cross_entropy import lm_head_ce, IGNORE_INDEX
-from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov
+from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov, frag_pseudograd, frag_outer_mix, \
+    SpanTable
 from .qcomm import pseudograd_q, qreduce, outer_nesterov_q
 from .determinism import set_deterministic, deterministic
 from . import reference
@@ -22,4 +23,4 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
            "lm_head_ce",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
-           "outer_nesterov_q", "reference"]
+           "outer_nesterov_q", "frag_pseudograd", "frag_outer_mix", "SpanTable", "reference"]

@@ -168,6 +168,9 @@ def _declare(L: ctypes.CDLL):
         "nd_pseudograd": [P, P, P, I, L64, P],
         "nd_outer_nesterov": [P, P, P, I, P, P, I, L64, F, F, F, I, P, P, P],
         "nd_axpby": [P, P, L64, F, F, P],
+        # streaming DiLoCo: fragment outer step through a span table (csrc/stream_outer.hip)
+        "nd_frag_pseudograd": [P, P, P, I, L64, P, I, P],
+        "nd_frag_outer_mix": [P, P, P, I, P, P, I, P, I, L64, F, F, F, I, F, P],
         # block-quantised outer transport (csrc/qcomm.hip)
         "nd_pseudograd_q": [P, P, L64, P, L64, L64, I, P],
         "nd_qreduce": [P, I, L64, I, P, P],

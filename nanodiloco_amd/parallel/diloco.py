@@ -24,7 +24,15 @@ Extensions (north star):
   in a checkpoint.  Not with ``overlap=True`` yet;
 * ``overlap=True``: the all-reduce is launched at the boundary and overlaps the next inner step;
   it is applied one step late as theta <- theta_outer + (theta_local_now - theta_local_boundary)
-  (streaming / delayed outer update).  ``overlap=False`` is bit-faithful to the reference order;
+  (the DELAYED outer update: one burst, one step late).  ``overlap=False`` is bit-faithful to the reference order;
+* ``fragments=P`` (Streaming DiLoCo, Douillard et al. 2025; ``parallel/fragments.py``, docs/DESIGN.md §4): the
+  model is cut into P fragments of whole layers, fragment p is sent after inner step t when
+  ``t % H == ((p+1)*H // P) % H`` (peak bytes 1/P of the burst), its all-reduce overlaps ``stream_overlap`` = tau
+  inner steps, and the result is merged into the drifting local weights as
+  ``(1 - alpha) * theta_new + alpha * theta_local`` (``stream_alpha``).  One ``nd_frag_pseudograd`` and one
+  ``nd_frag_outer_mix`` launch per fragment sync (csrc/stream_outer.hip), each fragment with its own momentum
+  history and ``first`` flag.  Driven by :meth:`Diloco.stream_step`; not with ``overlap``, the quantised
+  transports, ``offload_snapshot`` or ``inner_dp > 1``;
 * ``inner_dp > 1`` (two-level): the W/K workers' outer all-reduce is sharded over the K GPUs of a
   worker (each reduces 1/K of the pseudo-gradient over its outer group, then the worker
   all-gathers the updated weights), so cross-worker bytes per GPU drop by K.
@@ -42,6 +50,7 @@ from ..optim import FlatAdamW, FlatOuterNesterov
 from ..utils.schedule import CosineWarmupSchedule
 from .comm import FlatCommunicator, PendingAllReduce, plan_buckets
 from .dist import DistEnv
+from .fragments import PATTERNS, fragment_due, plan_fragments
 from ..ops import qcomm
 
 
@@ -72,6 +81,9 @@ class Diloco:
     def __new__(cls, model, *args, **kwargs):
         if not isinstance(model, LlamaForCausalLM):
             from .module_diloco import ModuleDiloco
+            if kwargs.get("fragments"):
+                raise ValueError("Streaming DiLoCo (fragments > 0) needs the flat-store Llama of Diloco: "
+                                 "ModuleDiloco does not take the streaming options")
             return ModuleDiloco(model, *args, **kwargs)
         return super().__new__(cls)
 
@@ -79,7 +91,8 @@ class Diloco:
                  warmup_steps: int, total_steps: int, inner_steps: int = 100, outer_steps: Optional[int] = None,
                  env: Optional[DistEnv] = None, comm_dtype: torch.dtype = torch.float32, bucket_mb: float = 128.0,
                  overlap: bool = False, offload_snapshot: bool = False, debug_checks: bool = False,
-                 broadcast_init: bool = True):
+                 broadcast_init: bool = True, fragments: int = 0, fragment_pattern: str = "strided",
+                 stream_overlap: int = 0, stream_alpha: float = 0.0):
         self.model = model
         self.store = model.store
         self.inner_optimizer = inner_optimizer
@@ -96,6 +109,12 @@ class Diloco:
         self.overlap = overlap
         self.offload_snapshot = offload_snapshot
         self.debug_checks = debug_checks
+        self.fragments = int(fragments)
+        self.fragment_pattern = fragment_pattern
+        self.stream_overlap = int(stream_overlap)
+        self.stream_alpha = float(stream_alpha)
+        if self.fragments:
+            self._check_streaming(model.config.num_hidden_layers)
         e = self.env
         f = e.force_collectives
         kw = dict(impl=e.comm_impl, device=e.device, timeout_s=e.timeout_s)
@@ -125,6 +144,12 @@ class Diloco:
             # the fp32 pseudo-gradient is never materialised: it is quantised in registers into the wire buffers
             self.delta = torch.zeros(0, dtype=torch.float32, device=self.store.device)
             self._qplan = self._plan_quantised(b - a)
+        elif self.fragments:
+            # ONE wire buffer, sized to the largest fragment: at most one fragment is ever in flight
+            plan = plan_fragments(self.store, model.config.num_hidden_layers, self.fragments, fragment_pattern)
+            self.frag_tables = [ops.SpanTable(sp, self.store.device) for sp in plan]
+            self.delta = torch.zeros(max(t.total for t in self.frag_tables), dtype=comm_dtype,
+                                     device=self.store.device)
         else:
             self.delta = torch.zeros(b - a, dtype=comm_dtype, device=self.store.device)
         self.drift_base = torch.zeros(b - a, dtype=torch.float32, device=self.store.device) if overlap else None
@@ -134,6 +159,31 @@ class Diloco:
         self._comm_events = []
         self.local_step = 0
         self.outer_step_count = 0
+        # streaming state: per-fragment step counters (the `first` flag and the momentum history are per
+        # fragment), the fragment in flight, the last one sent (for the byte / bucket properties)
+        self.frag_steps = [0] * self.fragments
+        self.fragment_sync_count = 0
+        self._stream_pending = None
+        self._last_frag = None
+        self._flushed = True  # no fragment sent yet: local weights == theta_sync on every worker
+
+    def _check_streaming(self, num_layers: int):
+        P, H, tau, alpha = self.fragments, self.inner_steps, self.stream_overlap, self.stream_alpha
+        if self.fragment_pattern not in PATTERNS:
+            raise ValueError(f"fragment_pattern must be one of {PATTERNS}, not {self.fragment_pattern!r}")
+        if not 1 <= P <= min(num_layers, H):
+            raise ValueError(f"fragments must be in [1, min(num_layers={num_layers}, inner_steps={H})], got {P}")
+        if not 0 <= tau < H // P:
+            raise ValueError(f"stream_overlap must be in [0, inner_steps // fragments = {H // P}), got {tau}: a "
+                             f"fragment must be applied before the next one is sent")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"stream_alpha must be in [0, 1], got {alpha}")
+        for on, what in ((self.overlap, "overlap=True (--overlap-outer)"),
+                         (bool(self.qbits), "quantised transport (comm_dtype int8 / int4)"),
+                         (self.offload_snapshot, "offload_snapshot=True (--offload-snapshot)"),
+                         (self.env.inner_dp > 1, "inner_dp > 1 (--inner-dp)")):
+            if on:
+                raise ValueError(f"Streaming DiLoCo (fragments > 0) is not supported together with {what}")
 
     # ------------------------------------------------------------------ reference API
     def __call__(self, *args, **kwargs):
@@ -155,6 +205,9 @@ class Diloco:
         """Pseudo-gradient payload each GPU contributes to the outer all-reduce."""
         if self.qbits:  # phase-1 (all-to-all) wire bytes: codes + scales of every chunk, padding included
             return sum(bk.send.numel() for bk in self._qplan) if self.outer_comm.enabled else 0
+        if self.fragments:  # the fragment sent last: the PEAK of a streaming run is what gets logged
+            n = self.frag_tables[self._last_frag].total if self._last_frag is not None else 0
+            return n * self.delta.element_size() if self.outer_comm.enabled else 0
         a, b = self.my_shard
         return (b - a) * torch.tensor([], dtype=self.comm_dtype).element_size() if self.outer_comm.enabled else 0
 
@@ -175,6 +228,9 @@ class Diloco:
             return 0
         if self.qbits:  # each bucket issues two collectives: an all-to-all and an all-gather
             return len(self._qplan)
+        if self.fragments:
+            n = self.frag_tables[self._last_frag].total if self._last_frag is not None else 0
+            return len(plan_buckets(0, n, self.delta.element_size(), self.outer_comm.bucket_bytes))
         a, b = self.my_shard
         return len(plan_buckets(0, b - a, self.delta.element_size(), self.outer_comm.bucket_bytes))
 
@@ -202,6 +258,9 @@ class Diloco:
         serialized -- every bucket's all-reduce completes before the first Nesterov update -- and
         records HIP events between the phases, so :meth:`outer_phase_ms` can split the step into
         pseudo-gradient / collective / outer-update time; the default pipelines buckets instead."""
+        if self.fragments:
+            raise RuntimeError("streaming mode (fragments > 0): call stream_step(t) after every inner step and "
+                               "flush_fragments() at the end instead of outer_step()")
         t0 = time.perf_counter()
         cuda = self.store.device.type == "cuda"
         ev0 = torch.cuda.Event(enable_timing=True) if cuda else None
@@ -359,6 +418,121 @@ class Diloco:
             marks.append(self._comm_events[-1][1])
             self._phase_marks = marks
 
+    # ------------------------------------------------------------------ streaming DiLoCo
+    def stream_step(self, t: int) -> Optional[dict]:
+        """Streaming mode: call after inner step ``t`` (1-based).  Applies the fragment whose overlap window ends
+        here (sent after step ``t - tau``), then sends the fragment that is due after step ``t`` (and, with
+        ``tau = 0``, applies it in the same call).  Returns ``{"sent": p or None, "applied": p or None}`` when
+        anything happened, else None."""
+        if not self.fragments:
+            raise RuntimeError("stream_step needs fragments > 0")
+        applied = sent = None
+        if self._stream_pending is not None and t >= self._stream_pending["apply_step"]:
+            applied = self._apply_fragment(self.stream_alpha)
+        p = fragment_due(t, self.inner_steps, self.fragments)
+        if p is not None:
+            self._send_fragment(p, t + self.stream_overlap)
+            sent = p
+            if self.stream_overlap == 0:
+                applied = self._apply_fragment(self.stream_alpha)
+        if sent is None and applied is None:
+            return None
+        return {"sent": sent, "applied": applied}
+
+    def _send_fragment(self, p: int, apply_step: int):
+        if self._stream_pending is not None:  # tau < H // P keeps the windows apart
+            raise RuntimeError(f"fragment {self._stream_pending['fragment']} is still in flight")
+        t0 = time.perf_counter()
+        cuda = self.store.device.type == "cuda"
+        ev0 = torch.cuda.Event(enable_timing=True) if cuda else None
+        if ev0 is not None:
+            ev0.record()
+        table = self.frag_tables[p]
+        wire = self.delta[:table.total]
+        ops.frag_pseudograd(self.sync, self.store.master, table, wire)
+        pend = self.outer_comm.all_reduce_async(wire)
+        self._stream_pending = {"fragment": p, "apply_step": apply_step, "pend": pend, "ev0": ev0}
+        self._last_frag = p
+        self._flushed = False
+        self.fragment_sync_count += 1
+        self._sync_time += time.perf_counter() - t0
+
+    def _apply_fragment(self, alpha: float, count_round: bool = True) -> int:
+        t0 = time.perf_counter()
+        st, self._stream_pending = self._stream_pending, None
+        p, pend, ev0 = st["fragment"], st["pend"], st["ev0"]
+        if ev0 is not None and self.stream_overlap > 0:
+            # the window in between belongs to the inner steps: time the apply alone
+            ev0 = torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        pend.wait_all()  # the compute stream waits for this fragment's buckets
+        opt, store = self.outer_optimizer, self.store
+        table = self.frag_tables[p]
+        ops.frag_outer_mix(store.master, self.sync, self.delta[:table.total], opt.momentum_buffer, store.shadow,
+                           table, 1.0 / max(1, self.env.num_workers), opt.lr, opt.momentum, self.frag_steps[p] == 0,
+                           alpha)
+        self.frag_steps[p] += 1
+        self.outer_comm.check("the fragment update")
+        store.version += 1
+        if count_round and p == self.fragments - 1:  # a round is complete
+            self.outer_step_count += 1
+            opt.step_count += 1
+        if ev0 is not None:
+            ev1 = torch.cuda.Event(enable_timing=True)
+            ev1.record()
+            self._comm_events = [(ev0, ev1)]
+        self._sync_time += time.perf_counter() - t0
+        self._sync_calls += 1
+        if self.debug_checks:
+            self.check_replicas()
+        return p
+
+    def flush_fragments(self):
+        """End of a streaming run: apply a pending fragment, then send and apply every fragment once with
+        tau = 0 and alpha = 0, so ``master == sync`` and all replicas are identical (an export-ready model).
+        The extra syncs do not count as outer steps."""
+        if not self.fragments:
+            return
+        if self._stream_pending is not None:
+            self._apply_fragment(self.stream_alpha)
+        for p in range(self.fragments):
+            self._send_fragment(p, 0)
+            self._apply_fragment(0.0, count_round=False)
+        self._flushed = True
+
+    @property
+    def streaming_local_weights(self) -> bool:
+        """Streaming mode between the first send and :meth:`flush_fragments`: every worker's local weights
+        carry its own inner progress (checkpoints keep them per rank and are not export-ready)."""
+        return bool(self.fragments) and not self._flushed
+
+    def pending_stream_state(self) -> Optional[dict]:
+        """The fragment in flight (a checkpoint inside its overlap window): the compute stream waits for its
+        all-reduce and the reduced packed buffer is returned WITHOUT applying it; None when nothing is pending."""
+        if self._stream_pending is None:
+            return None
+        st = self._stream_pending
+        st["pend"].wait_all()
+        return {"delta": self.delta[:self.frag_tables[st["fragment"]].total], "fragment": st["fragment"],
+                "apply_step": st["apply_step"]}
+
+    def restore_pending_stream(self, delta: torch.Tensor, fragment: int, apply_step: int):
+        """Re-arm the fragment saved by :meth:`pending_stream_state` (its all-reduce already done)."""
+        table = self.frag_tables[fragment]
+        wire = self.delta[:table.total]
+        wire.copy_(delta)
+        ranges = plan_buckets(0, table.total, wire.element_size(), self.outer_comm.bucket_bytes)
+        self._stream_pending = {"fragment": int(fragment), "apply_step": int(apply_step),
+                                "pend": PendingAllReduce([None] * len(ranges), ranges, wire), "ev0": None}
+        self._last_frag = int(fragment)
+        self._flushed = False
+
+    def streaming_config(self) -> Optional[dict]:
+        if not self.fragments:
+            return None
+        return {"fragments": self.fragments, "pattern": self.fragment_pattern, "overlap": self.stream_overlap,
+                "alpha": self.stream_alpha}
+
     def _sync_on_device(self) -> torch.Tensor:
         if not self.offload_snapshot:
             return self.sync
@@ -370,6 +544,8 @@ class Diloco:
         """Apply a still-pending overlapped outer step (end of training / before checkpoint)."""
         if self._pending is not None:
             self._finish_outer()
+        if self._stream_pending is not None:
+            self._apply_fragment(self.stream_alpha)
 
     def pending_outer_state(self) -> Optional[dict]:
         """An overlapped outer step that is still in flight (a checkpoint between the boundary and its
@@ -414,15 +590,15 @@ class Diloco:
         * theta_sync is identical on every rank of the job;
         * the GPUs of one DiLoCo worker (inner DDP) hold identical master weights;
         * without the overlapped outer step, the master weights equal theta_sync everywhere.
-        (In the overlapped mode the local weights legitimately differ across workers by each
-        worker's in-flight inner progress.)"""
+        (In the overlapped mode, and in the streaming mode until ``flush_fragments``, the local weights
+        legitimately differ across workers by each worker's in-flight inner progress.)"""
         if not self.env.is_distributed:
             return
         spread = self._checksum_spread(self.sync.to(self.store.device), None)
         if spread.max().item() > tol:
             raise RuntimeError(f"DiLoCo replicas diverged: theta_sync checksum spread {spread.tolist()}")
         self.check_inner_replicas(tol)
-        if not self.overlap and self._pending is None:
+        if not self.overlap and self._pending is None and not self.streaming_local_weights:
             spread = self._checksum_spread(self.store.master, None)
             if spread.max().item() > tol:
                 raise RuntimeError(f"DiLoCo replicas diverged: master checksum spread {spread.tolist()}")
@@ -449,6 +625,7 @@ class Diloco:
             "scheduler": self.scheduler.state_dict(),
             "local_step": self.local_step,
             "outer_step_count": self.outer_step_count,
+            "frag_steps": list(self.frag_steps),
         }
 
     def load_state_dict(self, d):
@@ -460,3 +637,5 @@ class Diloco:
         self.scheduler.load_state_dict(d["scheduler"])
         self.local_step = int(d["local_step"])
         self.outer_step_count = int(d["outer_step_count"])
+        if self.fragments and "frag_steps" in d:
+            self.frag_steps = [int(x) for x in d["frag_steps"]]

@@ -64,6 +64,11 @@ class TrainArgs:
     bucket_mb: float = 128.0
     overlap_outer: bool = False
     offload_snapshot: bool = False
+    streaming_fragments: int = 0   # Streaming DiLoCo (parallel/fragments.py): P fragments of whole layers, each
+                                   # synchronised every --inner-steps steps at staggered offsets (0 = off)
+    streaming_pattern: str = "strided"   # strided | sequential: which layers form a fragment
+    streaming_overlap_steps: int = 0     # tau: inner steps a fragment's all-reduce overlaps before it is applied
+    streaming_alpha: float = 0.0         # merge: (1 - alpha) * theta_new + alpha * theta_local (0.5 with tau >= 1)
     legacy_grad_sum: bool = False
     activation_checkpointing: bool = False
     residual_dtype: str = "auto"   # fp32 (the autocast recipe) | bf16: residual stream in bf16 (Megatron's default;
@@ -225,7 +230,12 @@ class Trainer:
         self.diloco = Diloco(self.model, inner, outer, a.warmup_steps, a.total_steps, a.inner_steps, self.outer_steps,
                              env=e, comm_dtype=_comm_dtype(a.comm_dtype, e.device), bucket_mb=a.bucket_mb,
                              overlap=a.overlap_outer, offload_snapshot=a.offload_snapshot,
-                             debug_checks=a.debug_checks)
+                             debug_checks=a.debug_checks, fragments=a.streaming_fragments,
+                             fragment_pattern=a.streaming_pattern, stream_overlap=a.streaming_overlap_steps,
+                             stream_alpha=a.streaming_alpha)
+        if a.streaming_fragments and a.elastic_resume:
+            raise ValueError("--elastic-resume is not supported with --streaming-fragments: a streaming checkpoint "
+                             "holds per-worker local weights")
         self.inner_sync = InnerGradSync(self.model, self.diloco.inner_comm)
         self.loss_scale = (1.0 if a.legacy_grad_sum else 1.0 / self.grad_accum) / e.inner_dp
         self.data = build_data(self.data_kind, vocab_size=self.llama_config.vocab_size, seq_len=a.seq_length,
@@ -322,7 +332,11 @@ class Trainer:
             loss = self.inner_step()
             real_step = step + 1
             did_outer = real_step % a.inner_steps == 0
-            if did_outer:
+            frag_event = None
+            if a.streaming_fragments:
+                with self.timer.phase("outer"):
+                    frag_event = self.diloco.stream_step(real_step)
+            elif did_outer:
                 with self.timer.phase("outer"):
                     self.diloco.outer_step()
             if prof_ctx is not None and step + 1 >= prof_at + a.profile_steps:
@@ -347,7 +361,9 @@ class Trainer:
                 }
                 if a.skip_nonfinite:
                     metrics["skipped_steps"] = int(self.diloco.inner_optimizer.skipped_steps.item())
-                if did_outer:
+                if frag_event is not None:
+                    metrics["fragment"] = frag_event["sent"] if frag_event["sent"] is not None else frag_event["applied"]
+                if frag_event is not None or (did_outer and not a.streaming_fragments):
                     metrics["bytes_outer"] = self.diloco.bytes_per_outer_step
                     metrics["sync_s"] = self.diloco.avg_sync_time
                     metrics["comm_ms"] = self.diloco.comm_ms()
@@ -359,7 +375,10 @@ class Trainer:
             if a.stop_at_step and real_step >= a.stop_at_step:
                 break
             _maybe_inject_fault(e.rank, real_step)
-        self.diloco.finalize()
+        if a.streaming_fragments and not a.stop_at_step:
+            self.diloco.flush_fragments()  # every fragment once more: master == theta_sync on every worker
+        else:
+            self.diloco.finalize()
         if a.checkpoint_dir and not a.stop_at_step:
             self.save(a.total_steps)
         if e.rank == 0:

@@ -18,6 +18,15 @@ without the pending outer update), and config.json says so (``"nanodiloco_pendin
 evaluation / export use a checkpoint without that flag -- the final one (``Diloco.finalize`` applies the
 pending step first) or any checkpoint of a run without ``--overlap-outer``.
 
+With ``--streaming-fragments`` (Streaming DiLoCo) the local weights of the workers differ between the first fragment
+sync and ``Diloco.flush_fragments``: every rank file carries its ``master``; when a fragment is inside its overlap
+window, also ``stream.delta`` (the reduced packed pseudo-gradient) and, in ``rank{r}.json``, the pending fragment
+index with its apply step, so the resumed run applies it at the same step.  ``trainer_state.json`` records
+``streaming: {fragments, pattern, overlap, alpha, frag_steps, ...}`` -- resume refuses a mismatch of any of the four
+options, a streaming checkpoint without the flags (and the converse) and ``--elastic-resume`` -- and ``config.json``
+says ``"nanodiloco_streaming_local_weights": true`` (not export-ready, like the pending-step flag).  The final
+checkpoint is written after the flush and carries neither.
+
 Crash consistency (round 5): every rank writes into ``<dir>.tmp``; after a barrier rank 0 adds
 ``COMPLETE.json`` and swaps the staging directory in (``<dir>`` -> ``<dir>.old``, ``<dir>.tmp`` -> ``<dir>``,
 then ``<dir>.old`` is removed), so a crash at any point of a save leaves the previous complete checkpoint
@@ -91,6 +100,9 @@ def _load_st(path: str) -> Dict[str, torch.Tensor]:
 def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_state: Optional[Dict[str, Any]] = None,
                     extra: Optional[Dict[str, Any]] = None):
     pending = diloco.pending_outer_state()  # overlapped mode: saved as pending, not applied
+    streaming = diloco.streaming_config() if hasattr(diloco, "streaming_config") else None
+    stream_pending = diloco.pending_stream_state() if streaming else None
+    stream_local = bool(streaming) and diloco.streaming_local_weights
     if env.inner_dp > 1:
         # two-level mode: each GPU of a worker updates only its shard of the outer momentum
         # (parallel/diloco.py, sharded outer step); gather the worker's full buffer before rank 0
@@ -113,6 +125,12 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
         per["outer.delta"] = pending["delta"]
         per["outer.drift_base"] = pending["drift_base"]
         per["master"] = store.master
+    if streaming:
+        per["master"] = store.master  # local weights differ per worker until flush_fragments
+        if stream_pending is not None:
+            per["stream.delta"] = stream_pending["delta"]
+            scal["stream_pending_fragment"] = stream_pending["fragment"]
+            scal["stream_apply_step"] = stream_pending["apply_step"]
     if data_state:
         for k, v in data_state.items():
             if isinstance(v, torch.Tensor):
@@ -126,6 +144,8 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
         cfg_json = model.config.to_hf_json()
         if pending is not None:  # see the module doc: weights are rank 0's local ones, not the synced model
             cfg_json["nanodiloco_pending_outer_step"] = True
+        if stream_local:  # rank 0's local weights, fragments at different sync ages: not the synced model either
+            cfg_json["nanodiloco_streaming_local_weights"] = True
         with open(os.path.join(ckpt_dir, "config.json"), "w") as f:
             json.dump(cfg_json, f, indent=2)
         _save_st(os.path.join(ckpt_dir, "model.safetensors"), {n: store.master_view(n) for n in store.names})
@@ -136,6 +156,11 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
                  "outer_opt_step": diloco.outer_optimizer.step_count, "scheduler": diloco.scheduler.state_dict(),
                  "world_size": env.world_size, "inner_dp": env.inner_dp, "flat_numel": store.numel,
                  "pending_outer": pending is not None, **(extra or {})}
+        if streaming:
+            state["streaming"] = {**streaming, "frag_steps": list(diloco.frag_steps),
+                                  "fragment_sync_count": diloco.fragment_sync_count, "local_weights": stream_local,
+                                  "pending_fragment": stream_pending["fragment"] if stream_pending else None,
+                                  "pending_apply_step": stream_pending["apply_step"] if stream_pending else None}
         with open(os.path.join(ckpt_dir, "trainer_state.json"), "w") as f:
             json.dump(state, f, indent=2)
     barrier(env)  # every rank's files are in the staging directory
@@ -170,6 +195,22 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     store = model.store
     old_world = int(state.get("world_size", env.world_size))
     resized = elastic and old_world != env.world_size
+    streamed = state.get("streaming")
+    want = diloco.streaming_config() if hasattr(diloco, "streaming_config") else None
+    if streamed and elastic:
+        raise ValueError(f"checkpoint {ckpt_dir} was written by a streaming run (per-worker local weights): "
+                         f"--elastic-resume is not supported for it")
+    if streamed and not want:
+        raise ValueError(f"checkpoint {ckpt_dir} was written with --streaming-fragments {streamed['fragments']}: "
+                         f"resume with the same streaming options")
+    if want and not streamed:
+        raise ValueError(f"checkpoint {ckpt_dir} was written without streaming: resume without "
+                         f"--streaming-fragments")
+    if want:
+        for key in ("fragments", "pattern", "overlap", "alpha"):
+            if streamed.get(key) != want[key]:
+                raise ValueError(f"checkpoint {ckpt_dir} was written with streaming {key}={streamed.get(key)!r}, "
+                                 f"this run has {want[key]!r}: resume needs the same streaming options")
     if resized:
         if env.inner_dp != 1 or int(state.get("inner_dp", 1)) != 1:
             raise ValueError("--elastic-resume needs one GPU per worker (--inner-dp 1) in both runs")
@@ -205,6 +246,16 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
             store.master.copy_(per["master"].to(store.master.device))
             diloco.restore_pending_outer(per["outer.delta"].to(diloco.delta.device),
                                          per["outer.drift_base"].to(diloco.delta.device))
+        if streamed:
+            store.master.copy_(per["master"].to(store.master.device))
+            diloco.frag_steps = [int(x) for x in streamed["frag_steps"]]
+            diloco.fragment_sync_count = int(streamed.get("fragment_sync_count", 0))
+            diloco._flushed = not streamed.get("local_weights", True)
+            if "stream.delta" in per:
+                with open(rfile[:-len(".safetensors")] + ".json") as f:
+                    sj = json.load(f)
+                diloco.restore_pending_stream(per["stream.delta"].to(diloco.delta.device),
+                                              int(sj["stream_pending_fragment"]), int(sj["stream_apply_step"]))
         diloco.inner_optimizer.exp_avg.copy_(per["adamw.exp_avg"])
         diloco.inner_optimizer.exp_avg_sq.copy_(per["adamw.exp_avg_sq"])
         with open(rfile[:-len(".safetensors")] + ".json") as f:
