@@ -5,6 +5,10 @@
 //   nd_qreduce           W received chunks -> one requantised chunk holding their sum (rank order)
 //   nd_outer_nesterov_q  the outer Nesterov update with d = (code * scale) * inv_w from the gathered chunks
 //
+// Error feedback (docs/DESIGN.md "Error feedback"): nd_pseudograd_q_ef / nd_qreduce_ef are the same kernels with
+// an fp32 residual added to the value before it is quantised and rewritten, in place, as what the codes did
+// not deliver: x = v + e, e = x - code * scale.  A lane reads and writes only its own four residual elements.
+//
 // One wave64 owns one quantisation block: lane l holds elements 4l..4l+3 (one float4), the block amax is a
 // wave reduction (no LDS, no barrier).  A 256-thread workgroup therefore covers four blocks per pass; the
 // grid is capped at 2048 workgroups like the other flat kernels and strides over the rest.
@@ -48,10 +52,11 @@ unsigned q_grid(int64_t nblk) {
 
 // Quantise the wave's block (x: this lane's 4 values) and store codes + scale.  fmaxf drops NaNs, so
 // non-finite values are tracked apart: such a block gets a NaN scale (and zero codes), and the update
-// that consumes it becomes NaN as it would with fp32 transport.
+// that consumes it becomes NaN as it would with fp32 transport.  Hands back the lane's codes (q) and returns
+// the block scale (wave-uniform) for the error-feedback residual.
 template <int BITS>
-__device__ __forceinline__ void quant_store(const float (&x)[4], uint8_t* __restrict__ codes,
-                                            float* __restrict__ scale, int lane) {
+__device__ __forceinline__ float quant_store(const float (&x)[4], uint8_t* __restrict__ codes,
+                                             float* __restrict__ scale, int lane, int (&q)[4]) {
   constexpr float QMAX = Q<BITS>::QMAX;
   const float m = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
   const bool bad = __any(!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]) && isfinite(x[3])));
@@ -59,7 +64,6 @@ __device__ __forceinline__ void quant_store(const float (&x)[4], uint8_t* __rest
   // IEEE division; kept finite: below amax ~ 3.7e-37 the quotient overflows, and a zero element times inf
   // would be NaN (with the clamp such a block only loses resolution, at a scale of ~1e-39)
   const float inv = (!bad && amax > 0.f) ? fminf(QMAX / amax, 3.402823466e+38f) : 0.f;
-  int q[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     q[k] = bad ? 0 : (int)fminf(fmaxf(rintf(x[k] * inv), -QMAX), QMAX);
@@ -73,7 +77,17 @@ __device__ __forceinline__ void quant_store(const float (&x)[4], uint8_t* __rest
     const uint32_t up = __shfl_xor(h, 1, 64);  // the pair's other half: even lanes store one dword
     if ((lane & 1) == 0) reinterpret_cast<uint32_t*>(codes)[lane >> 1] = h | (up << 16);
   }
-  if (lane == 0) scale[0] = bad ? __builtin_nanf("") : amax / QMAX;
+  const float sc = bad ? __builtin_nanf("") : amax / QMAX;
+  if (lane == 0) scale[0] = sc;
+  return sc;
+}
+
+// what the codes did not deliver: r = x - code * scale, product and difference rounded separately (the
+// receivers compute fl(code * scale)); a non-finite block (scale NaN) gives NaN
+__device__ __forceinline__ void residual_of(const float (&x)[4], const int (&q)[4], float sc, float (&r)[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = x[k] - (float)q[k] * sc;
 }
 
 // this lane's 4 codes of a block, as floats
@@ -90,10 +104,11 @@ __device__ __forceinline__ void load_codes(const uint8_t* __restrict__ codes, in
   }
 }
 
-template <int BITS>
+// EF: resid (n elements) is added to sync - master before the quantiser and rewritten with the new residual
+template <int BITS, bool EF>
 __global__ void __launch_bounds__(256) pseudograd_q_kernel(const float* __restrict__ sync, const float* __restrict__ p,
-                                                           int64_t n, uint8_t* __restrict__ out, int64_t nblk,
-                                                           int64_t bpc) {
+                                                           float* __restrict__ resid, int64_t n,
+                                                           uint8_t* __restrict__ out, int64_t nblk, int64_t bpc) {
   const Wire w = wire_of<BITS>(bpc);
   const int lane = threadIdx.x & 63;
   for (int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); blk < nblk; blk += (int64_t)gridDim.x * 4) {
@@ -103,20 +118,41 @@ __global__ void __launch_bounds__(256) pseudograd_q_kernel(const float* __restri
       const float4 S = *reinterpret_cast<const float4*>(sync + e);
       const float4 P = *reinterpret_cast<const float4*>(p + e);
       x[0] = S.x - P.x; x[1] = S.y - P.y; x[2] = S.z - P.z; x[3] = S.w - P.w;
+      if (EF) {
+        const float4 E = *reinterpret_cast<const float4*>(resid + e);
+        x[0] = x[0] + E.x; x[1] = x[1] + E.y; x[2] = x[2] + E.z; x[3] = x[3] + E.w;
+      }
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (e + k < n) x[k] = sync[e + k] - p[e + k];
+        if (e + k < n) {
+          x[k] = sync[e + k] - p[e + k];
+          if (EF) x[k] = x[k] + resid[e + k];
+        }
     }
     const int64_t ch = blk / bpc, j = blk - ch * bpc;
     uint8_t* base = out + ch * w.stride;
-    quant_store<BITS>(x, base + j * Q<BITS>::BLOCK_BYTES, reinterpret_cast<float*>(base + w.code_bytes) + j, lane);
+    int q[4];
+    const float sc = quant_store<BITS>(x, base + j * Q<BITS>::BLOCK_BYTES,
+                                       reinterpret_cast<float*>(base + w.code_bytes) + j, lane, q);
+    if (EF) {  // no residual past n: nothing is read or written there
+      float r[4];
+      residual_of(x, q, sc, r);
+      if (e + 4 <= n) {
+        *reinterpret_cast<float4*>(resid + e) = make_float4(r[0], r[1], r[2], r[3]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (e + k < n) resid[e + k] = r[k];
+      }
+    }
   }
 }
 
-template <int BITS>
+// EF: resid (one chunk, bpc * 256 elements) is added after the rank-order sum and rewritten
+template <int BITS, bool EF>
 __global__ void __launch_bounds__(256) qreduce_kernel(const uint8_t* __restrict__ in, int nw, int64_t bpc,
-                                                      uint8_t* __restrict__ out) {
+                                                      float* __restrict__ resid, uint8_t* __restrict__ out) {
   const Wire w = wire_of<BITS>(bpc);
   const int lane = threadIdx.x & 63;
   for (int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < bpc; j += (int64_t)gridDim.x * 4) {
@@ -133,7 +169,19 @@ __global__ void __launch_bounds__(256) qreduce_kernel(const uint8_t* __restrict_
         for (int k = 0; k < 4; ++k) acc[k] = acc[k] + v[k] * sc;
       }
     }
-    quant_store<BITS>(acc, out + j * Q<BITS>::BLOCK_BYTES, reinterpret_cast<float*>(out + w.code_bytes) + j, lane);
+    float4* E = EF ? reinterpret_cast<float4*>(resid + j * QB + lane * 4) : nullptr;
+    if (EF) {
+      const float4 e = *E;
+      acc[0] = acc[0] + e.x; acc[1] = acc[1] + e.y; acc[2] = acc[2] + e.z; acc[3] = acc[3] + e.w;
+    }
+    int q[4];
+    const float sc = quant_store<BITS>(acc, out + j * Q<BITS>::BLOCK_BYTES,
+                                       reinterpret_cast<float*>(out + w.code_bytes) + j, lane, q);
+    if (EF) {
+      float r[4];
+      residual_of(acc, q, sc, r);
+      *E = make_float4(r[0], r[1], r[2], r[3]);
+    }
   }
 }
 
@@ -197,8 +245,21 @@ ND_API int nd_pseudograd_q(const float* sync, const float* p, int64_t n, void* o
   if (!aligned(sync, 16) || !aligned(p, 16) || !aligned(out, 4)) return (int)hipErrorInvalidValue;
   const int64_t nblk = nchunks * bpc;
   uint8_t* o = static_cast<uint8_t*>(out);
-  if (bits == 8) hipLaunchKernelGGL(pseudograd_q_kernel<8>, dim3(q_grid(nblk)), dim3(256), 0, s, sync, p, n, o, nblk, bpc);
-  else hipLaunchKernelGGL(pseudograd_q_kernel<4>, dim3(q_grid(nblk)), dim3(256), 0, s, sync, p, n, o, nblk, bpc);
+  float* none = nullptr;
+  if (bits == 8) hipLaunchKernelGGL((pseudograd_q_kernel<8, false>), dim3(q_grid(nblk)), dim3(256), 0, s, sync, p, none, n, o, nblk, bpc);
+  else hipLaunchKernelGGL((pseudograd_q_kernel<4, false>), dim3(q_grid(nblk)), dim3(256), 0, s, sync, p, none, n, o, nblk, bpc);
+  ND_LAUNCH_CHECK();
+}
+
+// nd_pseudograd_q of fl(fl(sync - master) + resid); resid (n fp32, 16-byte aligned) becomes x - code * scale
+ND_API int nd_pseudograd_q_ef(const float* sync, const float* p, float* resid, int64_t n, void* out, int64_t nchunks,
+                              int64_t bpc, int bits, hipStream_t s) {
+  if ((bits != 8 && bits != 4) || n < 0 || nchunks < 1 || bpc < 1 || n > nchunks * bpc * QB) return (int)hipErrorInvalidValue;
+  if (!resid || !aligned(resid, 16) || !aligned(sync, 16) || !aligned(p, 16) || !aligned(out, 4)) return (int)hipErrorInvalidValue;
+  const int64_t nblk = nchunks * bpc;
+  uint8_t* o = static_cast<uint8_t*>(out);
+  if (bits == 8) hipLaunchKernelGGL((pseudograd_q_kernel<8, true>), dim3(q_grid(nblk)), dim3(256), 0, s, sync, p, resid, n, o, nblk, bpc);
+  else hipLaunchKernelGGL((pseudograd_q_kernel<4, true>), dim3(q_grid(nblk)), dim3(256), 0, s, sync, p, resid, n, o, nblk, bpc);
   ND_LAUNCH_CHECK();
 }
 
@@ -208,8 +269,20 @@ ND_API int nd_qreduce(const void* in, int nw, int64_t bpc, int bits, void* out, 
   if (!aligned(in, 4) || !aligned(out, 4)) return (int)hipErrorInvalidValue;
   const uint8_t* i = static_cast<const uint8_t*>(in);
   uint8_t* o = static_cast<uint8_t*>(out);
-  if (bits == 8) hipLaunchKernelGGL(qreduce_kernel<8>, dim3(q_grid(bpc)), dim3(256), 0, s, i, nw, bpc, o);
-  else hipLaunchKernelGGL(qreduce_kernel<4>, dim3(q_grid(bpc)), dim3(256), 0, s, i, nw, bpc, o);
+  float* none = nullptr;
+  if (bits == 8) hipLaunchKernelGGL((qreduce_kernel<8, false>), dim3(q_grid(bpc)), dim3(256), 0, s, i, nw, bpc, none, o);
+  else hipLaunchKernelGGL((qreduce_kernel<4, false>), dim3(q_grid(bpc)), dim3(256), 0, s, i, nw, bpc, none, o);
+  ND_LAUNCH_CHECK();
+}
+
+// nd_qreduce of fl(sum + resid); resid (one chunk: bpc * 256 fp32, 16-byte aligned) becomes x - code * scale
+ND_API int nd_qreduce_ef(const void* in, int nw, int64_t bpc, int bits, float* resid, void* out, hipStream_t s) {
+  if ((bits != 8 && bits != 4) || nw < 1 || nw > 64 || bpc < 1) return (int)hipErrorInvalidValue;
+  if (!resid || !aligned(resid, 16) || !aligned(in, 4) || !aligned(out, 4)) return (int)hipErrorInvalidValue;
+  const uint8_t* i = static_cast<const uint8_t*>(in);
+  uint8_t* o = static_cast<uint8_t*>(out);
+  if (bits == 8) hipLaunchKernelGGL((qreduce_kernel<8, true>), dim3(q_grid(bpc)), dim3(256), 0, s, i, nw, bpc, resid, o);
+  else hipLaunchKernelGGL((qreduce_kernel<4, true>), dim3(q_grid(bpc)), dim3(256), 0, s, i, nw, bpc, resid, o);
   ND_LAUNCH_CHECK();
 }
 

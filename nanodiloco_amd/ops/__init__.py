@@ -13,7 +13,7 @@ from .attention import attention, rope_cache, set_attn_fused_stats, key_start, c
 from .cross_entropy import lm_head_ce, IGNORE_INDEX
 from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov, frag_pseudograd, frag_outer_mix, \
     SpanTable
-from .qcomm import pseudograd_q, qreduce, outer_nesterov_q
+from .qcomm import pseudograd_q, qreduce, outer_nesterov_q, pseudograd_q_ef, qreduce_ef
 from .determinism import set_deterministic, deterministic
 from . import reference
 
@@ -23,4 +23,4 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
            "lm_head_ce",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
-           "outer_nesterov_q", "frag_pseudograd", "frag_outer_mix", "SpanTable", "reference"]
+           "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "frag_pseudograd", "frag_outer_mix", "SpanTable", "reference"]

@@ -174,6 +174,8 @@ def _declare(L: ctypes.CDLL):
         # block-quantised outer transport (csrc/qcomm.hip)
         "nd_pseudograd_q": [P, P, L64, P, L64, L64, I, P],
         "nd_qreduce": [P, I, L64, I, P, P],
+        "nd_pseudograd_q_ef": [P, P, P, L64, P, L64, L64, I, P],
+        "nd_qreduce_ef": [P, I, L64, I, P, P, P],
         "nd_outer_nesterov_q": [P, P, P, I, L64, P, P, I, L64, F, F, F, I, P],
         # fp8 quantisation
         "nd_fp8_cast": [P, I, L64, P, P, I, P, I, P],

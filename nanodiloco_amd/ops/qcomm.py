@@ -15,6 +15,11 @@ One wire chunk of ``c`` elements (a multiple of 256) is ``[codes: c*bits/8 bytes
 a wire buffer is ``nchunks`` chunks back to back (uint8).  int4 codes are two's-complement nibbles, element
 2i in the low nibble of byte i.
 
+Error feedback (``pseudograd_q_ef`` / ``qreduce_ef``, docs/DESIGN.md "Error feedback"): the same two stages with
+an fp32 residual ``e`` carried across outer steps -- ``x = fl(v + e)`` is quantised instead of ``v`` and
+``e = fl(x - fl(code * scale))`` is what the receivers did not get.  With ``e = 0`` the wire bytes are those of
+the stateless functions.
+
 Every function has a PyTorch implementation with the identical operation order (CPU path).
 """
 from __future__ import annotations
@@ -121,6 +126,34 @@ def pseudograd_q(sync: torch.Tensor, master: torch.Tensor, out: torch.Tensor, nc
     _store(out, nchunks, c, bits, codes, scale)
 
 
+def _residual(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """x fp32 ``[nb, 256]`` minus what its codes deliver: ``x - code * scale``, two roundings (NaN for a NaN scale)."""
+    return x - codes.float() * scale[:, None]
+
+
+def pseudograd_q_ef(sync: torch.Tensor, master: torch.Tensor, resid: torch.Tensor, out: torch.Tensor, nchunks: int,
+                    c: int, bits: int) -> None:
+    """:func:`pseudograd_q` with error feedback: quantises ``(sync - master) + resid`` and rewrites ``resid``
+    (fp32, ``master.numel()`` elements) in place with ``x - code * scale``.  Padding past the span holds no residual."""
+    n = master.numel()
+    pb = chunk_bytes(c, bits)
+    if sync.numel() != n or n > nchunks * c or out.numel() != nchunks * pb or out.dtype != torch.uint8:
+        raise ValueError("pseudograd_q_ef: span / wire buffer sizes do not match")
+    if resid.numel() != n or resid.dtype != torch.float32 or not resid.is_contiguous() or resid.device != master.device:
+        raise ValueError("pseudograd_q_ef: the residual is a contiguous fp32 tensor of the span's length")
+    if _ext.use_hip(master):
+        _ext.check(_ext.lib().nd_pseudograd_q_ef(_ext.ptr(sync), _ext.ptr(master), _ext.ptr(resid), n, _ext.ptr(out),
+                                                 nchunks, c // QBLOCK, bits, _ext.stream_ptr(master.device)),
+                   "nd_pseudograd_q_ef")
+        return
+    x = torch.zeros(nchunks * c, dtype=torch.float32, device=master.device)
+    torch.sub(sync, master, out=x[:n])
+    x[:n] += resid
+    codes, scale = _quantize_blocks(x.view(-1, QBLOCK), bits)
+    _store(out, nchunks, c, bits, codes, scale)
+    resid.copy_(_residual(x.view(-1, QBLOCK), codes, scale).view(-1)[:n])
+
+
 def qreduce(inp: torch.Tensor, nw: int, c: int, bits: int, out: torch.Tensor) -> None:
     """``inp``: ``nw`` received chunks in worker-rank order; ``out``: one chunk, the requantised
     ``sum_w code_w * scale_w`` (fp32, summed in rank order)."""
@@ -138,6 +171,29 @@ def qreduce(inp: torch.Tensor, nw: int, c: int, bits: int, out: torch.Tensor) ->
         acc = acc + _unpack(codes[w], bits) * scales[w].repeat_interleave(QBLOCK)
     q, scale = _quantize_blocks(acc.view(-1, QBLOCK), bits)
     _store(out, 1, c, bits, q, scale)
+
+
+def qreduce_ef(inp: torch.Tensor, nw: int, c: int, bits: int, resid: torch.Tensor, out: torch.Tensor) -> None:
+    """:func:`qreduce` with error feedback: the rank-order sum first, then ``+ resid`` (fp32, ``c`` elements), which
+    is rewritten in place with what the requantised chunk does not deliver."""
+    pb = chunk_bytes(c, bits)
+    if not 1 <= nw <= 64 or inp.numel() != nw * pb or out.numel() != pb or out.dtype != torch.uint8 \
+            or inp.dtype != torch.uint8:
+        raise ValueError("qreduce_ef: wire buffer sizes do not match")
+    if resid.numel() != c or resid.dtype != torch.float32 or not resid.is_contiguous() or resid.device != inp.device:
+        raise ValueError("qreduce_ef: the residual is a contiguous fp32 tensor of one chunk's length")
+    if _ext.use_hip(inp):
+        _ext.check(_ext.lib().nd_qreduce_ef(_ext.ptr(inp), nw, c // QBLOCK, bits, _ext.ptr(resid), _ext.ptr(out),
+                                            _ext.stream_ptr(inp.device)), "nd_qreduce_ef")
+        return
+    codes, scales = wire_views(inp, nw, c, bits)
+    acc = torch.zeros(c, dtype=torch.float32, device=inp.device)
+    for w in range(nw):
+        acc = acc + _unpack(codes[w], bits) * scales[w].repeat_interleave(QBLOCK)
+    x = (acc + resid).view(-1, QBLOCK)
+    q, scale = _quantize_blocks(x, bits)
+    _store(out, 1, c, bits, q, scale)
+    resid.copy_(_residual(x, q, scale).view(-1))
 
 
 def outer_nesterov_q(master: torch.Tensor, sync: torch.Tensor, gathered: torch.Tensor, nchunks: int, c: int, bits: int,

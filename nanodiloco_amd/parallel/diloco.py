@@ -20,8 +20,11 @@ Extensions (north star):
 * ``comm_dtype="int8"`` / ``"int4"`` (``torch.int8`` = ``"int8"``): block-quantised transport, a quarter /
   an eighth of the fp32 bytes.  Integers with per-block scales cannot be all-reduced, so the step becomes
   ``nd_pseudograd_q`` -> all-to-all -> ``nd_qreduce`` -> all-gather -> ``nd_outer_nesterov_q`` per bucket
-  (a quantised reduce-scatter + all-gather, docs/DESIGN.md §4).  Stateless: no error feedback, nothing new
-  in a checkpoint.  Not with ``overlap=True`` yet;
+  (a quantised reduce-scatter + all-gather, docs/DESIGN.md §4).  Stateless by default; ``error_feedback=True``
+  keeps two fp32 residuals per GPU -- ``qef_send`` (what this worker's codes did not deliver, one element per
+  element of the owned span) and ``qef_reduce`` (the same for the chunk it requantises, per bucket) -- adds them
+  before the next step's quantisation (``nd_pseudograd_q_ef`` / ``nd_qreduce_ef``) and stores them in the
+  per-rank checkpoint files.  Not with ``overlap=True`` yet;
 * ``overlap=True``: the all-reduce is launched at the boundary and overlaps the next inner step;
   it is applied one step late as theta <- theta_outer + (theta_local_now - theta_local_boundary)
   (the DELAYED outer update: one burst, one step late).  ``overlap=False`` is bit-faithful to the reference order;
@@ -84,6 +87,9 @@ class Diloco:
             if kwargs.get("fragments"):
                 raise ValueError("Streaming DiLoCo (fragments > 0) needs the flat-store Llama of Diloco: "
                                  "ModuleDiloco does not take the streaming options")
+            if kwargs.pop("error_feedback", False):
+                raise ValueError("error_feedback belongs to the quantised transport (comm_dtype int8 / int4), which "
+                                 "needs the flat-store Llama of Diloco: ModuleDiloco does not take it")
             return ModuleDiloco(model, *args, **kwargs)
         return super().__new__(cls)
 
@@ -92,7 +98,7 @@ class Diloco:
                  env: Optional[DistEnv] = None, comm_dtype: torch.dtype = torch.float32, bucket_mb: float = 128.0,
                  overlap: bool = False, offload_snapshot: bool = False, debug_checks: bool = False,
                  broadcast_init: bool = True, fragments: int = 0, fragment_pattern: str = "strided",
-                 stream_overlap: int = 0, stream_alpha: float = 0.0):
+                 stream_overlap: int = 0, stream_alpha: float = 0.0, error_feedback: bool = False):
         self.model = model
         self.store = model.store
         self.inner_optimizer = inner_optimizer
@@ -105,6 +111,10 @@ class Diloco:
         if self.qbits and overlap:
             raise ValueError("quantised transport (comm_dtype int8 / int4) does not support overlap=True yet: the "
                              "delayed application and its pending-state checkpoint need the fp32 / bf16 path")
+        if error_feedback and not self.qbits:
+            raise ValueError("error_feedback=True (--comm-error-feedback) needs the quantised transport: comm_dtype "
+                             f"'int8' or 'int4', not {comm_dtype}")
+        self.error_feedback = bool(error_feedback)
         self.comm_dtype = comm_dtype
         self.overlap = overlap
         self.offload_snapshot = offload_snapshot
@@ -144,6 +154,13 @@ class Diloco:
             # the fp32 pseudo-gradient is never materialised: it is quantised in registers into the wire buffers
             self.delta = torch.zeros(0, dtype=torch.float32, device=self.store.device)
             self._qplan = self._plan_quantised(b - a)
+            if self.error_feedback:
+                # fp32 residuals, zero at the start: one element per owned element, and one chunk per bucket (a
+                # single allocation, bucket i's view at _qef_views[i]) for the chunk this worker requantises
+                dev = self.store.device
+                self.qef_send = torch.zeros(b - a, dtype=torch.float32, device=dev)
+                self.qef_reduce = torch.zeros(sum(bk.c for bk in self._qplan), dtype=torch.float32, device=dev)
+                self._qef_views = list(self.qef_reduce.split([bk.c for bk in self._qplan]))
         elif self.fragments:
             # ONE wire buffer, sized to the largest fragment: at most one fragment is ever in flight
             plan = plan_fragments(self.store, model.config.num_hidden_layers, self.fragments, fragment_pattern)
@@ -376,7 +393,9 @@ class Diloco:
         all-gather -> update.  Every bucket's quantise + all-to-all is issued first, then each bucket is
         reduced and its all-gather issued, then each bucket is updated while the next one is still being
         gathered; the host never blocks (GPU).  EVERY worker, the owner of a chunk included, updates from
-        the gathered bytes, so theta_sync and the master stay bit-identical across workers."""
+        the gathered bytes, so theta_sync and the master stay bit-identical across workers.  With
+        ``error_feedback`` the two quantising ops are their ``_ef`` forms, which carry ``qef_send`` /
+        ``qef_reduce``; nothing else in the step changes."""
         e, opt, bits = self.env, self.outer_optimizer, self.qbits
         w, r = max(1, e.num_workers), e.worker
         a, _ = self.my_shard
@@ -385,6 +404,7 @@ class Diloco:
         first = opt.step_count == 0
         inv_w = 1.0 / w
         comm = self.outer_comm
+        ef = self.error_feedback
 
         def mark():
             ev = torch.cuda.Event(enable_timing=True)
@@ -394,14 +414,20 @@ class Diloco:
         exchanged = []
         for bk in self._qplan:
             ga, gb = a + bk.x, a + bk.y
-            ops.pseudograd_q(sync[ga:gb], master[ga:gb], bk.send, w, bk.c, bits)
+            if ef:
+                ops.pseudograd_q_ef(sync[ga:gb], master[ga:gb], self.qef_send[bk.x:bk.y], bk.send, w, bk.c, bits)
+            else:
+                ops.pseudograd_q(sync[ga:gb], master[ga:gb], bk.send, w, bk.c, bits)
             exchanged.append(comm.all_to_all_async(bk.send, bk.recv))
         marks = [ev0, mark()] if phases else None
         gathered = []
-        for bk, work in zip(self._qplan, exchanged):
+        for i, (bk, work) in enumerate(zip(self._qplan, exchanged)):
             work.wait()
             pb = bk.send.numel() // w
-            ops.qreduce(bk.recv, w, bk.c, bits, bk.gath[r * pb:(r + 1) * pb])
+            if ef:
+                ops.qreduce_ef(bk.recv, w, bk.c, bits, self._qef_views[i], bk.gath[r * pb:(r + 1) * pb])
+            else:
+                ops.qreduce(bk.recv, w, bk.c, bits, bk.gath[r * pb:(r + 1) * pb])
             gathered.append(comm.all_gather_async(bk.gath, r))
         if phases:
             for work in gathered:
@@ -417,6 +443,50 @@ class Diloco:
         if phases:
             marks.append(self._comm_events[-1][1])
             self._phase_marks = marks
+
+    def error_feedback_state(self) -> Optional[dict]:
+        """The residuals of the quantised transport for a checkpoint (per rank): ``send`` / ``reduce`` and what
+        they are indexed by -- ``bits``, ``num_workers`` and the bucket ``plan`` ``[[x, y, c], ...]``.  None
+        without ``error_feedback``."""
+        if not self.error_feedback:
+            return None
+        return {"send": self.qef_send, "reduce": self.qef_reduce, "bits": self.qbits,
+                "num_workers": max(1, self.env.num_workers), "plan": [[bk.x, bk.y, bk.c] for bk in self._qplan]}
+
+    def load_error_feedback_state(self, send: Optional[torch.Tensor], reduce: Optional[torch.Tensor],
+                                  meta: Optional[dict]) -> list:
+        """Restore the residuals saved by :meth:`error_feedback_state`; returns the lines worth logging.
+
+        * no saved residuals (a stateless checkpoint, or a worker the checkpoint did not have): both start at zero;
+        * ``send`` is indexed by element of the owned span: restored whenever its length matches, also across
+          int8 <-> int4 (it is an fp32 amount still owed, whatever step size it was measured with);
+        * ``reduce`` is indexed by bucket and chunk: restored only when the saved ``plan`` and ``num_workers``
+          equal this run's, else zero (an elastic resume always changes the plan);
+        * without ``error_feedback`` saved residuals are ignored.
+
+        A dropped residual costs at most half a quantisation step per element, once: it is the part of earlier
+        pseudo-gradients that would have been delivered later, and nothing else depends on it."""
+        if not self.error_feedback:
+            return ["checkpoint holds error-feedback residuals; this run has no --comm-error-feedback: ignored"] \
+                if send is not None or reduce is not None else []
+        notes = []
+        self.qef_send.zero_()
+        self.qef_reduce.zero_()
+        if send is None and reduce is None:
+            return ["no error-feedback residuals in the checkpoint for this rank: starting from zero"]
+        if send is not None and send.numel() == self.qef_send.numel():
+            self.qef_send.copy_(send)
+        elif send is not None:
+            notes.append(f"qef.send has {send.numel()} elements, this rank owns {self.qef_send.numel()}: starting "
+                         f"from zero")
+        mine = self.error_feedback_state()
+        same = meta is not None and int(meta.get("num_workers", -1)) == mine["num_workers"] \
+            and [list(map(int, p)) for p in meta.get("plan", [])] == mine["plan"]
+        if reduce is not None and same and reduce.numel() == self.qef_reduce.numel():
+            self.qef_reduce.copy_(reduce)
+        elif reduce is not None:
+            notes.append("qef.reduce was saved for another bucket plan or worker count: starting from zero")
+        return notes
 
     # ------------------------------------------------------------------ streaming DiLoCo
     def stream_step(self, t: int) -> Optional[dict]:

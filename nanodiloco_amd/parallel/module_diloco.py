@@ -89,7 +89,10 @@ class ModuleDiloco:
                  outer_optimizer: torch.optim.Optimizer, warmup_steps: int, total_steps: int,
                  inner_steps: int = 100, outer_steps: int = 10, comm_dtype: Optional[torch.dtype] = None,
                  offload_snapshot: bool = False, bucket_mb: float = 128.0, max_grad_norm: float = 1.0,
-                 broadcast_init: bool = True):
+                 broadcast_init: bool = True, error_feedback: bool = False):
+        if error_feedback:
+            raise ValueError("error_feedback belongs to the quantised transport (comm_dtype int8 / int4), which needs "
+                             "the flat-store Llama of Diloco: ModuleDiloco does not take it")
         if comm_dtype in ("int8", "int4", torch.int8):
             raise ValueError("quantised transport (comm_dtype int8 / int4) needs the flat-store Llama of Diloco: "
                              "ModuleDiloco carries fp32 / bf16 pseudo-gradients only")

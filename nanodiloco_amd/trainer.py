@@ -61,6 +61,8 @@ class TrainArgs:
     max_grad_norm: float = 1.0
     weight_decay: float = 0.01
     comm_dtype: str = "fp32"       # fp32 | bf16 | int8 | int4 (block-quantised outer transport, parallel/diloco.py)
+    comm_error_feedback: bool = False  # with int8 | int4: carry what quantisation did not deliver into the next
+                                       # outer step (two fp32 residuals per GPU, docs/DESIGN.md "Error feedback")
     bucket_mb: float = 128.0
     overlap_outer: bool = False
     offload_snapshot: bool = False
@@ -193,6 +195,9 @@ class Trainer:
         self.args = a = args
         if a.total_steps % a.inner_steps:
             raise ValueError("total_steps must be a multiple of inner_steps")  # REF main.py:69
+        if a.comm_error_feedback and a.comm_dtype not in ("int8", "int4"):
+            raise ValueError(f"--comm-error-feedback needs the quantised transport (--comm-dtype int8 | int4), not "
+                             f"--comm-dtype {a.comm_dtype}: fp32 / bf16 pseudo-gradients are all-reduced as they are")
         ops.set_backend(a.ops)
         ops.set_wgrad_overlap(a.wgrad_overlap)
         ops.set_deterministic(a.deterministic)
@@ -232,7 +237,7 @@ class Trainer:
                              overlap=a.overlap_outer, offload_snapshot=a.offload_snapshot,
                              debug_checks=a.debug_checks, fragments=a.streaming_fragments,
                              fragment_pattern=a.streaming_pattern, stream_overlap=a.streaming_overlap_steps,
-                             stream_alpha=a.streaming_alpha)
+                             stream_alpha=a.streaming_alpha, error_feedback=a.comm_error_feedback)
         if a.streaming_fragments and a.elastic_resume:
             raise ValueError("--elastic-resume is not supported with --streaming-fragments: a streaming checkpoint "
                              "holds per-worker local weights")

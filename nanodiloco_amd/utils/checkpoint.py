@@ -27,6 +27,14 @@ options, a streaming checkpoint without the flags (and the converse) and ``--ela
 says ``"nanodiloco_streaming_local_weights": true`` (not export-ready, like the pending-step flag).  The final
 checkpoint is written after the flush and carries neither.
 
+With ``--comm-error-feedback`` (quantised transport with residuals, parallel/diloco.py) every rank file carries
+``qef.send`` and ``qef.reduce``, and ``trainer_state.json`` records ``comm_error_feedback: {bits, num_workers, plan}``
+(the bucket plan ``[[x, y, c], ...]`` that ``qef.reduce`` is laid out by).  The residuals are an optimisation state
+that may be dropped (``Diloco.load_error_feedback_state`` has the rules and the cost): a stateless checkpoint
+resumes with the flag on from zero residuals, a checkpoint with residuals resumes without the flag and ignores
+them, ``qef.send`` survives int8 <-> int4 and ``--elastic-resume`` (surviving ranks; new workers start at zero),
+``qef.reduce`` only an unchanged plan and worker count.
+
 Crash consistency (round 5): every rank writes into ``<dir>.tmp``; after a barrier rank 0 adds
 ``COMPLETE.json`` and swaps the staging directory in (``<dir>`` -> ``<dir>.old``, ``<dir>.tmp`` -> ``<dir>``,
 then ``<dir>.old`` is removed), so a crash at any point of a save leaves the previous complete checkpoint
@@ -103,6 +111,7 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
     streaming = diloco.streaming_config() if hasattr(diloco, "streaming_config") else None
     stream_pending = diloco.pending_stream_state() if streaming else None
     stream_local = bool(streaming) and diloco.streaming_local_weights
+    qef = diloco.error_feedback_state() if hasattr(diloco, "error_feedback_state") else None
     if env.inner_dp > 1:
         # two-level mode: each GPU of a worker updates only its shard of the outer momentum
         # (parallel/diloco.py, sharded outer step); gather the worker's full buffer before rank 0
@@ -131,6 +140,8 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
             per["stream.delta"] = stream_pending["delta"]
             scal["stream_pending_fragment"] = stream_pending["fragment"]
             scal["stream_apply_step"] = stream_pending["apply_step"]
+    if qef is not None:
+        per["qef.send"], per["qef.reduce"] = qef["send"], qef["reduce"]
     if data_state:
         for k, v in data_state.items():
             if isinstance(v, torch.Tensor):
@@ -161,6 +172,8 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
                                   "fragment_sync_count": diloco.fragment_sync_count, "local_weights": stream_local,
                                   "pending_fragment": stream_pending["fragment"] if stream_pending else None,
                                   "pending_apply_step": stream_pending["apply_step"] if stream_pending else None}
+        if qef is not None:
+            state["comm_error_feedback"] = {k: qef[k] for k in ("bits", "num_workers", "plan")}
         with open(os.path.join(ckpt_dir, "trainer_state.json"), "w") as f:
             json.dump(state, f, indent=2)
     barrier(env)  # every rank's files are in the staging directory
@@ -185,7 +198,8 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     (SURVEY.md §5.3).  Data: the memmap stream is global (csrc/runtime/token_loader.cpp), so every worker
     restarts it where the old workers stopped together (``data_state_rank0``; nothing repeated or skipped);
     the HF loader's contiguous shards cannot be re-cut exactly and the resume refuses; synthetic workers keep
-    their own random stream (new ones draw a fresh one)."""
+    their own random stream (new ones draw a fresh one).  Error-feedback residuals: surviving ranks keep their
+    ``qef.send``, new workers and every ``qef.reduce`` start at zero (``Diloco.load_error_feedback_state``)."""
     found = find_checkpoint(ckpt_dir)
     if found is None:
         raise FileNotFoundError(f"no complete checkpoint at {ckpt_dir}")
@@ -236,6 +250,7 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     rfile = os.path.join(ckpt_dir, f"rank{env.rank}.safetensors")
     data_state: Dict[str, Any] = {}
     own = os.path.exists(rfile)
+    qef_send = qef_reduce = None
     if not own and resized:  # a worker the checkpoint did not have: rank 0's AdamW state, fresh data stream
         rfile = os.path.join(ckpt_dir, "rank0.safetensors")
     elif not own and "world_size" in state:
@@ -262,12 +277,20 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
             scal = json.load(f)
         diloco.inner_optimizer.step_count = int(scal["adamw_step"])
         if own:
+            qef_send, qef_reduce = per.get("qef.send"), per.get("qef.reduce")
             for k, v in per.items():
                 if k.startswith("data."):
                     data_state[k[5:]] = v
             for k, v in scal.items():
                 if k.startswith("data."):
                     data_state[k[5:]] = v
+    if hasattr(diloco, "load_error_feedback_state"):
+        saved = state.get("comm_error_feedback")
+        had = saved is not None or qef_send is not None
+        if had or diloco.error_feedback:
+            for line in diloco.load_error_feedback_state(qef_send, qef_reduce, saved):
+                if env.rank == 0 or (diloco.error_feedback and had and qef_send is None):
+                    print(f"[resume] rank {env.rank}: {line}", flush=True)
     state["data_state"] = data_state
     if resized:
         # the data sources whose stream is global (memmap) restart every worker -- survivors and new ones --

@@ -5,7 +5,9 @@ process with the kernels they stand beside: ``nd_pseudograd`` (bf16 out) and ``n
 All are HBM streams, so the figure of merit is achieved bytes/s over the bytes each kernel MUST move
 (computed from the shapes below), and the expectation is parity with the baselines' bytes/s.  HIP events
 around ``--iters`` back-to-back launches, every arm warmed up, arms alternated over ``--rounds`` rounds, median
-reported (docs/PROFILING.md).  Prints a markdown table; ``--out`` also writes the bare table to a file of its
+reported (docs/PROFILING.md).  The error-feedback kernels (``nd_pseudograd_q_ef``, ``nd_qreduce_ef``) stand next
+to their stateless siblings and are compared with them: they move the residual in and out on top, 4 + 4 bytes per
+element (16 instead of 8 bytes of fp32 per element for the quantiser; both in addition to the wire bytes).  Prints a markdown table; ``--out`` also writes the bare table to a file of its
 own (profiles/qcomm_kernels.md is hand-written around a copy of it: paste the table there, do not point
 ``--out`` at it).
 
@@ -46,6 +48,7 @@ def main():
     mom = torch.zeros(n, device=dev)
     shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
     delta_bf16 = torch.zeros(n, dtype=torch.bfloat16, device=dev)
+    resid1 = torch.zeros(n, device=dev)  # error-feedback residuals: they evolve over the launches, the bytes do not
     arms = {}  # name -> (callable, bytes it must move, baseline name or None)
     arms["nd_pseudograd (bf16 out)"] = (lambda: ops.pseudograd(sync, master, delta_bf16), 8 * n + 2 * n, None)
     arms["nd_outer_nesterov (bf16 in)"] = (
@@ -57,6 +60,9 @@ def main():
         arms[f"nd_pseudograd_q int{bits}"] = (
             lambda wire=wire, c1=c1, bits=bits: ops.pseudograd_q(sync, master, wire, 1, c1, bits), 8 * n + wb,
             "nd_pseudograd (bf16 out)")
+        arms[f"nd_pseudograd_q_ef int{bits}"] = (
+            lambda wire=wire, c1=c1, bits=bits: ops.pseudograd_q_ef(sync, master, resid1, wire, 1, c1, bits), 16 * n + wb,
+            f"nd_pseudograd_q int{bits}")
         cw = qcomm.chunk_elems(n, W)  # the chunk one worker owns; it receives W of them
         pb = qcomm.chunk_bytes(cw, bits)
         recv = torch.zeros(W * pb, dtype=torch.uint8, device=dev)
@@ -67,6 +73,10 @@ def main():
         arms[f"nd_qreduce int{bits} (W = {W})"] = (
             lambda recv=recv, cw=cw, bits=bits, red=red: ops.qreduce(recv, W, cw, bits, red), recv.numel() + red.numel(),
             "nd_pseudograd (bf16 out)")
+        resid2 = torch.zeros(cw, device=dev)
+        arms[f"nd_qreduce_ef int{bits} (W = {W})"] = (
+            lambda recv=recv, cw=cw, bits=bits, red=red, resid2=resid2: ops.qreduce_ef(recv, W, cw, bits, resid2, red),
+            recv.numel() + red.numel() + 8 * cw, f"nd_qreduce int{bits} (W = {W})")
         arms[f"nd_outer_nesterov_q int{bits}"] = (
             lambda wire=wire, c1=c1, bits=bits: ops.outer_nesterov_q(master, sync, wire, 1, c1, bits, mom, shadow, 1.0 / W,
                                                                      1e-9, 0.9, False), wb + 8 * n + 14 * n,
