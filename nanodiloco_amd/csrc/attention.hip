@@ -26,6 +26,7 @@
 // Causal: tiles past the diagonal are never loaded; fully masked (wave, tile) pairs are skipped;
 // the longest query / key blocks are dispatched first.
 #include "lds_dma.h"
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1199,7 +1200,8 @@ __global__ void __launch_bounds__(256, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_kernel
 }
 
 // ------------------------------------------------------------------------------------ launchers
-// Launch-time switches, read ONCE when the library loads (never per launch).  Only correct variants are
+// Launch-time switches, parsed when the library loads (never per launch; nd_env_reload() in env.hip runs the
+// same parse again, for tests that flip a switch inside one process).  Only correct variants are
 // selectable in the product library; the wrong-result timing ablations (ABL bits other than the
 // forward's 32) are compiled only into a -DND_ABLATION build (`python -m nanodiloco_amd.csrc.build
 // --ablation` -> _lib/alt/libnd_kernels_ablation.so), so a stray ND_ATTN_*ABL variable cannot change
@@ -1219,7 +1221,7 @@ struct AttnEnv {
   bool dkdv_bq64 = false;  // ND_DKDV_BQ=64: 64-query tiles (unfused backward)
   int fwd_abl = 0, dkdv_abl = 0;  // ND_ATTN_ABL / ND_ATTN_DKDV_ABL timing ablations: ND_ABLATION builds only
 };
-static const AttnEnv g_attn = [] {
+static AttnEnv parse_attn_env() {
   AttnEnv c;
   auto s = [](const char* k) { return getenv(k); };
   if (const char* e = s("ND_ATTN_ORDER")) c.order = atoi(e);
@@ -1243,7 +1245,20 @@ static const AttnEnv g_attn = [] {
   if (const char* e = s("ND_ATTN_DKDV_ABL")) c.dkdv_abl = atoi(e);
 #endif
   return c;
-}();
+}
+static AttnEnv g_attn = parse_attn_env();
+namespace nd {
+void attn_env_reload() { g_attn = parse_attn_env(); }
+int attn_env_describe(char* buf, int n) {
+  const AttnEnv& c = g_attn;
+  return snprintf(buf, n > 0 ? n : 0,
+                  "ND_ATTN_ORDER=%d ND_ATTN_DKDV_ORDER=%d ND_ATTN_THR=%g ND_ATTN_FWD=%s ND_ATTN_ABL=%d ND_ATTN_FWD_W=%d "
+                  "ND_ATTN_DQ_W=%d ND_ATTN_DKDV_W=%d ND_ATTN_DKDV_NB=%d ND_ATTN_DKDV=%s ND_DKDV_BQ=%s ND_ATTN_DKDV_ABL=%d",
+                  c.order, c.dkdv_order, (double)c.thr, c.fwd_reg ? "r" : "d", c.fwd_abl ? c.fwd_abl : c.fwd_var,
+                  c.fwd_w8 ? 8 : 4, c.dq_w8 ? 8 : 4, c.dkdv_w8 ? 8 : 4, c.dkdv_nb, c.dkdv_reg ? "r" : "d",
+                  c.dkdv_bq64 ? "64" : "auto", c.dkdv_abl);
+}
+}  // namespace nd
 static int attn_order() { return g_attn.order; }
 // bit 0: a (batch, head)'s key blocks consecutive on one XCD (MHA only); bit 1: descending query walk
 // (LDS-DMA dK/dV kernel)

@@ -10,6 +10,7 @@
 // scale = loss_scale / n_valid lives in device memory (no host sync).  Rows whose target is
 // ignore_index contribute 0 loss and 0 gradient.  Larger vocabularies use the two-pass variant.
 #include "common.h"
+#include <cstdio>
 #include <cstdlib>
 
 using namespace nd;
@@ -236,11 +237,16 @@ __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logi
   }
 }
 
-// ND_CE=r: the register kernel for bf16 rows too (A/B), read once at load
-static const bool g_ce_reg = [] {
+// ND_CE=r: the register kernel for bf16 rows too (A/B), parsed at load (and by nd_env_reload(), env.hip)
+static bool parse_ce_env() {
   const char* e = getenv("ND_CE");
   return e && e[0] == 'r';
-}();
+}
+static bool g_ce_reg = parse_ce_env();
+namespace nd {
+void ce_env_reload() { g_ce_reg = parse_ce_env(); }
+int ce_env_describe(char* buf, int n) { return snprintf(buf, n > 0 ? n : 0, "ND_CE=%s", g_ce_reg ? "r" : "d"); }
+}  // namespace nd
 
 ND_API int nd_ce_fwd_bwd(void* logits, int dt, const int64_t* targets, float* loss_sum, const float* scale,
                          int64_t n, int V, int ignore, float* lse_out, float* row_loss, float /*reserved*/,

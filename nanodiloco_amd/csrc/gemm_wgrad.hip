@@ -29,6 +29,7 @@
 // Split count per launch: a fixed rule (~256 workgroups), replaced by a makespan model where it predicts a
 // >= 10 % win (plan() below).
 #include "lds_dma.h"
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -658,12 +659,13 @@ __global__ void __launch_bounds__(512, 1) wgrad8_pp_kernel(const uint8_t* __rest
 // a time below pct % of the fixed rule's (default 90; A/B of the threshold).  The model is only trusted for large
 // predicted gains: at 99 % it moves the Llama-150M q|k|v weight gradient from 5 to 16 splits (3 full waves) and
 // the bf16 step gets 2.1 % SLOWER (session r5al)
-static const double g_wgrad_plan_thr = [] {
+static double parse_wgrad_plan_thr() {
   const char* e = getenv("ND_WGRAD_PLAN");
   if (e && e[0] == 'o') return 0.0;
   if (e && e[0] == 'c' && atoi(e + 1) > 0) return atoi(e + 1) / 100.0;
   return 0.9;
-}();
+}
+static double g_wgrad_plan_thr = parse_wgrad_plan_thr();
 
 static int num_cus_wg() {
   static int n = [] {
@@ -771,18 +773,37 @@ static int fit_kchunk(int K, int* S, int bk) {
   }
 }
 
-// ND_WGRAD_VARIANT (A/B runs), read once at load; outside -DND_ABLATION builds the wrong-result forms
-// ("nodma", "a<bits>") are dropped, i.e. the default kernel runs
-static const char* wgrad_env() {
-  static const char* v = [] {
-    const char* e = getenv("ND_WGRAD_VARIANT");
+// ND_WGRAD_VARIANT (A/B runs), parsed at load (and by nd_env_reload(), env.hip); outside -DND_ABLATION builds
+// the wrong-result forms ("nodma", "a<bits>") are dropped, i.e. the default kernel runs.  The value is copied:
+// the pointer getenv returns does not survive a change of the environment.
+struct WgradVariant {
+  bool set = false;
+  char v[16] = {0};
+};
+static WgradVariant parse_wgrad_variant() {
+  WgradVariant r;
+  const char* e = getenv("ND_WGRAD_VARIANT");
 #ifndef ND_ABLATION
-    if (e && (e[0] == 'n' || e[0] == 'a')) return (const char*)nullptr;
+  if (e && (e[0] == 'n' || e[0] == 'a')) e = nullptr;
 #endif
-    return e;
-  }();
-  return v;
+  if (e) {
+    r.set = true;
+    strncpy(r.v, e, sizeof(r.v) - 1);
+  }
+  return r;
 }
+static WgradVariant g_wgrad_variant = parse_wgrad_variant();
+static const char* wgrad_env() { return g_wgrad_variant.set ? g_wgrad_variant.v : nullptr; }
+namespace nd {
+void wgrad_env_reload() {
+  g_wgrad_plan_thr = parse_wgrad_plan_thr();
+  g_wgrad_variant = parse_wgrad_variant();
+}
+int wgrad_env_describe(char* buf, int n) {
+  return snprintf(buf, n > 0 ? n : 0, "ND_WGRAD_VARIANT=%s ND_WGRAD_PLAN=%g", wgrad_env() && wgrad_env()[0] ? wgrad_env() : "default",
+                  g_wgrad_plan_thr);
+}
+}  // namespace nd
 
 // Number of K splits for this shape (slab workspace = S * M * N floats when S > 1).
 ND_API int nd_wgrad_splits(int M, int N, int K) {

@@ -130,6 +130,9 @@ def _declare(L: ctypes.CDLL):
     P, I, F, L64, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_double
     sigs = {
         "nd_version": [],
+        # A/B switches (csrc/env.hip): parse the ND_* environment again / the parsed state as text; tests only
+        "nd_env_reload": [],
+        "nd_env_describe": [P, I],
         # norms
         "nd_rmsnorm_fwd": [P, I, P, I, P, P, I, P, P, L64, I, F, P],
         "nd_rmsnorm_bwd": [P, I, P, I, P, P, P, P, I, P, L64, I, P, P],

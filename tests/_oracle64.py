@@ -2,9 +2,10 @@
 
 Every function here is plain PyTorch in float64, written from the math in the kernel headers
 (``csrc/norm.hip``, ``rope.hip``, ``swiglu.hip``, ``cross_entropy.hip``, ``embedding.hip``, ``optim.hip``,
-``transpose.hip``) and ``ops/reference.py``; none of them calls the code under test.  They run on whatever
+``transpose.hip``, ``attention.hip``) and ``ops/reference.py``; none of them calls the code under test.  They run on whatever
 device their inputs live on; ``tests/test_oracle64_cpu.py`` checks each against the project's torch twin
-on the CPU, ``tests/test_rowwise_edges_gpu.py`` uses them against the HIP kernels.
+on the CPU, ``tests/test_rowwise_edges_gpu.py`` and ``tests/test_attention_edges_gpu.py`` use them against the
+HIP kernels.
 
 The error rule (``check``), per element:
   output stored as bf16:  |out - ref64| <= 2^-8 * |ref64| + slack     (2^-8: half a bf16 ulp, relative)
@@ -140,6 +141,100 @@ def rope(qkv, cos, sin, B, T, nh, nkv, hd, inverse=False):
     x1, x2 = blk[..., :half], blk[..., half:]
     rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).reshape(B * T, nrot * hd)
     return torch.cat([rot, x[:, nrot * hd:]], dim=1)
+
+
+# ------------------------------------------------------------------------------------------ attention
+LOG2E = 1.4426950408889634
+
+
+def attention_mask(B, T, device, kstart=None, doc_start=None):
+    """Boolean [B, 1, T, T], True = query row attends to key column: key <= query, and key >= kstart[b] (left
+    padding) or key >= doc_start[b, query] (packed documents)."""
+    t = torch.arange(T, device=device)
+    ok = (t[None, :] <= t[:, None]).expand(B, T, T).clone()
+    if kstart is not None:
+        ok &= t.view(1, 1, T) >= kstart.to(device).long().view(B, 1, 1)
+    if doc_start is not None:
+        ok &= t.view(1, 1, T) >= doc_start.to(device).long().view(B, T, 1)
+    return ok.unsqueeze(1)
+
+
+def _attention(qkv, B, T, nh, nkv, hd, scale, kstart, doc_start, dO, rope_out, cos, sin, o_saved, rnd):
+    assert kstart is None or doc_start is None
+    x = qkv.double().view(B, T, (nh + 2 * nkv) * hd)
+    rep = nh // nkv
+    q = x[..., :nh * hd].reshape(B, T, nh, hd).transpose(1, 2)
+    k = x[..., nh * hd:(nh + nkv) * hd].reshape(B, T, nkv, hd).transpose(1, 2).repeat_interleave(rep, dim=1)
+    v = x[..., (nh + nkv) * hd:].reshape(B, T, nkv, hd).transpose(1, 2).repeat_interleave(rep, dim=1)
+    ok = attention_mask(B, T, qkv.device, kstart, doc_start)
+    s = (q @ k.transpose(-1, -2)) * scale
+    s = s.masked_fill(~ok, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    seen = torch.isfinite(m)  # rows with at least one key
+    p = torch.exp(s - torch.where(seen, m, torch.zeros_like(m)))  # unnormalised, masked keys exactly 0
+    l = p.sum(-1, keepdim=True)
+    l1 = torch.where(seen, l, torch.ones_like(l))
+    o = (rnd(p) @ v) / l1  # fully masked rows: 0
+    lse2 = ((m + torch.log(l)) * LOG2E)[..., 0]  # fully masked rows: -inf + log(0) = -inf
+
+    def rows(t4):  # [B, H, T, hd] -> [B*T, H*hd]
+        return t4.transpose(1, 2).reshape(B * T, -1)
+
+    out = {"o": rows(o), "lse2": lse2, "mask": ok, "seen": seen[:, 0, :, 0].expand(B, T)}
+    if dO is None:
+        return out
+    d = dO.double().view(B, T, nh, hd).transpose(1, 2)
+    ob = (rows(o).bfloat16() if o_saved is None else o_saved).double().view(B, T, nh, hd).transpose(1, 2)
+    delta = (d * ob).sum(-1)
+    P = p / l1
+    dv = rnd(P).transpose(-1, -2) @ d
+    dS = rnd(P * (d @ v.transpose(-1, -2) - delta[..., None]))
+    dq = scale * (dS @ k)
+    dk = scale * (dS.transpose(-1, -2) @ q)
+    dk = dk.view(B, nkv, rep, T, hd).sum(2)  # GQA: the group's query heads
+    dv = dv.view(B, nkv, rep, T, hd).sum(2)
+    dqkv = torch.cat([rows(dq), rows(dk), rows(dv)], dim=1)
+    if rope_out:
+        dqkv = rope(dqkv, cos, sin, B, T, nh, nkv, hd, inverse=True)
+    out.update(delta=delta, dqkv=dqkv, dq=dqkv[:, :nh * hd], dk=dqkv[:, nh * hd:(nh + nkv) * hd],
+               dv=dqkv[:, (nh + nkv) * hd:])
+    return out
+
+
+def attention(qkv, B, T, nh, nkv, hd, scale, kstart=None, doc_start=None, dO=None, rope_out=False, cos=None,
+              sin=None, o_saved=None):
+    """Causal attention on packed rows q|k|v [B*T, (nh + 2 nkv) * hd] AS THE KERNELS SEE THEM (q|k already rotated);
+    query head h uses kv head h // (nh / nkv).  Query q attends to keys lo <= k <= q with lo = 0, ``kstart[b]``
+    (int [B]) or ``doc_start[b, q]`` (int [B, T]).  s = scale * q k^T, P = softmax(s), o = P v; a query with no key
+    gives o = 0 and lse = -inf.  Returns float64: o [B*T, nh*hd], lse2 [B, nh, T] = logsumexp(s) * log2(e) (the
+    stored unit), mask [B, 1, T, T], seen [B, T] (the query has a key), and with ``dO`` [B*T, nh*hd]:
+      delta [B, nh, T] = rowsum(dO * o_bf16), o_bf16 = o rounded to bf16 as the forward saves it (``o_saved``: that
+      tensor given instead, for a kernel whose input it is);
+      dV = P^T dO, dP = dO V^T, dS = P * (dP - delta), dQ = scale dS K, dK = scale dS^T Q, dK / dV summed over the
+      query heads of a group; dq [B*T, nh*hd], dk, dv [B*T, nkv*hd] and the packed dqkv.
+    ``rope_out``: dq and dk go through the inverse rotation (``cos`` / ``sin``), as the store epilogues of
+    rope_mode 2 do -- the gradient with respect to the un-rotated q|k."""
+    return _attention(qkv, B, T, nh, nkv, hd, scale, kstart, doc_start, dO, rope_out, cos, sin, o_saved,
+                      lambda t: t)
+
+
+def attention_twin(qkv, B, T, nh, nkv, hd, scale, kstart=None, doc_start=None, dO=None, rope_out=False, cos=None,
+                   sin=None, o_saved=None):
+    """The error level of the kernels' number formats, nothing of their tiling or deferred max: the same float64
+    math with the operand roundings the kernel header documents -- P (unnormalised in the forward, its row sum l
+    taken from the unrounded P) rounded to bf16 before P V and before P^T dO, dS rounded to bf16 before dS K and
+    dS^T Q.  ``lse2`` and ``delta`` (fp32 outputs) are instead the plain fp32 PyTorch twin on the same inputs."""
+    out = _attention(qkv, B, T, nh, nkv, hd, scale, kstart, doc_start, dO, rope_out, cos, sin, o_saved,
+                     lambda t: t.bfloat16().double())
+    x = qkv.float().view(B, T, (nh + 2 * nkv) * hd)
+    q = x[..., :nh * hd].reshape(B, T, nh, hd).transpose(1, 2)
+    k = x[..., nh * hd:(nh + nkv) * hd].reshape(B, T, nkv, hd).transpose(1, 2).repeat_interleave(nh // nkv, dim=1)
+    s = (q @ k.transpose(-1, -2)) * f32_scalar(scale)
+    out["lse2"] = torch.logsumexp(s.masked_fill(~out["mask"], float("-inf")), dim=-1) * f32_scalar(LOG2E)
+    if dO is not None:
+        ob = attention(qkv, B, T, nh, nkv, hd, scale, kstart, doc_start)["o"].bfloat16() if o_saved is None else o_saved
+        out["delta"] = (dO.float() * ob.float()).view(B, T, nh, hd).sum(-1).transpose(1, 2)
+    return out
 
 
 # ------------------------------------------------------------------------------------------ SwiGLU

@@ -7,6 +7,8 @@ import torch
 from nanodiloco_amd import ops
 from nanodiloco_amd.ops import reference as ref
 
+from ._switches import switches
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -319,26 +321,26 @@ def test_outer_nesterov_matches_torch_sgd(comm):
                                    # Llama-1B: q|k|v, gate|up, down, lm head
                                    (2560, 2048, 8192), (11264, 2048, 4096), (2048, 5632, 4096), (32000, 2048, 2048)])
 @pytest.mark.parametrize("variant", ["", "dma0", "dmas", "b"])
-def test_wgrad_gemm(M, N, K, variant, monkeypatch):
-    monkeypatch.setenv("ND_WGRAD_VARIANT", variant)
+def test_wgrad_gemm(M, N, K, variant):
     from nanodiloco_amd.ops.gemm import wgrad
     dy = torch.randn(K, M, device=DEV).bfloat16()
     x = torch.randn(K, N, device=DEV).bfloat16()
     gw0 = torch.randn(M, N, device=DEV)
     gw = gw0.clone()
-    wgrad(gw, dy, x)
-    ref_ = gw0 + dy.float().t() @ x.float()
-    assert rel(gw, ref_) < 1e-5, rel(gw, ref_)
-    gw2 = gw0.clone()
-    wgrad(gw2, dy, x)
+    with switches(ND_WGRAD_VARIANT=variant) as state:
+        assert state["ND_WGRAD_VARIANT"] == (variant or "default")
+        wgrad(gw, dy, x)
+        ref_ = gw0 + dy.float().t() @ x.float()
+        assert rel(gw, ref_) < 1e-5, rel(gw, ref_)
+        gw2 = gw0.clone()
+        wgrad(gw2, dy, x)
     assert torch.equal(gw, gw2)  # deterministic (no atomics)
 
 
 @pytest.mark.parametrize("variant", ["", "dma0", "dmas", "b"])
-def test_wgrad_no_empty_split_with_poisoned_slabs(variant, monkeypatch):
+def test_wgrad_no_empty_split_with_poisoned_slabs(variant):
     """K = 41 * 64 over 16 output tiles: rounding the per-split K chunk up to whole tiles would leave the
     last split empty; its slab plane must not be summed stale (the workspace is NaN-poisoned first)."""
-    monkeypatch.setenv("ND_WGRAD_VARIANT", variant)
     from nanodiloco_amd.ops import gemm as G
     M = N = 1024
     K = 41 * 64
@@ -346,7 +348,9 @@ def test_wgrad_no_empty_split_with_poisoned_slabs(variant, monkeypatch):
     dy = torch.randn(K, M, device=DEV).bfloat16()
     x = torch.randn(K, N, device=DEV).bfloat16()
     gw = torch.zeros(M, N, device=DEV)
-    G.wgrad(gw, dy, x)
+    with switches(ND_WGRAD_VARIANT=variant) as state:
+        assert state["ND_WGRAD_VARIANT"] == (variant or "default")
+        G.wgrad(gw, dy, x)
     assert torch.isfinite(gw).all()
     assert rel(gw, dy.float().t() @ x.float()) < 1e-5
 
@@ -647,17 +651,16 @@ def _store_view(store, flat, name):
     (2, 320, 4, 4, 32, None), (2, 256, 4, 4, 64, (0, 100)), (2, 1024, 16, 16, 64, (0, 700)),
 ])
 @pytest.mark.parametrize("variant", ["d", "d8", "dx", "d8x", "r"])
-def test_attention_fwd_variants(B, T, nh, nkv, hd, pads, variant, monkeypatch):
+def test_attention_fwd_variants(B, T, nh, nkv, hd, pads, variant):
     """Forward kernels on pre-rotated q|k (the fused-RoPE path): the LDS-DMA kernel with 128- and
     256-query blocks ('d', 'd8'; 'x' = its cheaper-mask / split-sum variant) and the register-staged
     one ('r') against fp32 torch, output and log-sum-exp; T % 128 == 64 leaves idle waves in the last
     query block."""
     from nanodiloco_amd.ops import _ext
     from nanodiloco_amd.ops.attention import key_start
-    monkeypatch.setenv("ND_ATTN_ABL", "32" if variant.endswith("x") else "0")  # x: the ILP softmax variant
+    abl = "32" if variant.endswith("x") else "0"  # x: the ILP softmax variant
     variant = variant.rstrip("x")
-    monkeypatch.setenv("ND_ATTN_FWD", variant[0])
-    monkeypatch.setenv("ND_ATTN_FWD_W", variant[1:] if variant[0] == "d" and variant[1:] else "4")
+    width = variant[1:] if variant[0] == "d" and variant[1:] else "4"
     ld = (nh + 2 * nkv) * hd
     qkv = torch.randn(B * T, ld, device=DEV).bfloat16()
     qkv[T // 2, nh * hd:(nh + 1) * hd] *= 20  # a late key with a large score: deferred-max rescale path
@@ -671,9 +674,11 @@ def test_attention_fwd_variants(B, T, nh, nkv, hd, pads, variant, monkeypatch):
     o = torch.empty(B * T, nh * hd, device=DEV, dtype=torch.bfloat16)
     lse = torch.empty(B, nh, T, device=DEV)
     L = _ext.lib()
-    _ext.check(L.nd_attn_fwd_ks(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, nh, nkv, T,
-                                hd, ld, nh * hd, 0, 0, hd ** -0.5, ks.data_ptr() if ks is not None else 0,
-                                _ext.stream_ptr(qkv.device)), "fwd")
+    with switches(ND_ATTN_ABL=abl, ND_ATTN_FWD=variant[0], ND_ATTN_FWD_W=width) as state:
+        assert (state["ND_ATTN_ABL"], state["ND_ATTN_FWD"], state["ND_ATTN_FWD_W"]) == (abl, variant[0], width)
+        _ext.check(L.nd_attn_fwd_ks(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, nh, nkv,
+                                    T, hd, ld, nh * hd, 0, 0, hd ** -0.5, ks.data_ptr() if ks is not None else 0,
+                                    _ext.stream_ptr(qkv.device)), "fwd")
     q4, k4, v4 = ref.split_qkv(qkv.float(), B, T, nh, nkv, hd)
     rep = nh // nkv
     k4, v4 = k4.repeat_interleave(rep, 1), v4.repeat_interleave(rep, 1)
@@ -700,12 +705,12 @@ def test_attention_fwd_variants(B, T, nh, nkv, hd, pads, variant, monkeypatch):
     (2, 256, 4, 4, 64, (0, 100)), (2, 1024, 8, 2, 64, (0, 700)),
 ])
 @pytest.mark.parametrize("variant", ["o", "o8", "k8"])
-def test_attention_bwd_dq_variants(B, T, nh, nkv, hd, pads, variant, monkeypatch):
+def test_attention_bwd_dq_variants(B, T, nh, nkv, hd, pads, variant):
     """Fused backward (dQ kernel with the row statistics, then dK/dV) with 128- / 256-query dQ blocks
     ('o', 'o8') and 256-key dK/dV blocks ('k8'): all three gradients against fp32."""
     from nanodiloco_amd.ops.attention import key_start, rope_cache
-    monkeypatch.setenv("ND_ATTN_DQ_W", variant[1:] if variant[0] == "o" and variant[1:] else "4")
-    monkeypatch.setenv("ND_ATTN_DKDV_W", "8" if variant == "k8" else "4")  # 256-key dK/dV blocks
+    dq_w = variant[1:] if variant[0] == "o" and variant[1:] else "4"
+    dkdv_w = "8" if variant == "k8" else "4"  # 256-key dK/dV blocks
     ld = (nh + 2 * nkv) * hd
     ks = None
     if pads is not None:
@@ -716,11 +721,13 @@ def test_attention_bwd_dq_variants(B, T, nh, nkv, hd, pads, variant, monkeypatch
     qkv = torch.randn(B * T, ld, device=DEV).bfloat16()
     cos, sin = rope_cache(T, hd, 10000.0, None, DEV)
     x = qkv.clone().requires_grad_(True)
-    o = ops.attention(x, cos, sin, B, T, nh, nkv, hd, kstart=ks)
     xr = qkv.float().requires_grad_(True)
     orf = ref.attention_block(xr, cos, sin, B, T, nh, nkv, hd, kstart=ks)
     do = torch.randn_like(orf)
-    o.backward(do.bfloat16())
+    with switches(ND_ATTN_DQ_W=dq_w, ND_ATTN_DKDV_W=dkdv_w) as state:
+        assert (state["ND_ATTN_DQ_W"], state["ND_ATTN_DKDV_W"]) == (dq_w, dkdv_w)
+        o = ops.attention(x, cos, sin, B, T, nh, nkv, hd, kstart=ks)
+        o.backward(do.bfloat16())
     orf.backward(do.bfloat16().float())
     g, gr = x.grad.float(), xr.grad
     assert torch.isfinite(g).all()
@@ -734,7 +741,7 @@ def test_attention_bwd_dq_variants(B, T, nh, nkv, hd, pads, variant, monkeypatch
     (2, 1024, 8, 2, 64, (0, 700)),
 ])
 @pytest.mark.parametrize("nb", ["2", "3", "4"])
-def test_attention_dkdv_prefetch_depth_bitwise(B, T, nh, nkv, hd, pads, nb, monkeypatch):
+def test_attention_dkdv_prefetch_depth_bitwise(B, T, nh, nkv, hd, pads, nb):
     """dK/dV with 64-query tiles and NB LDS buffers (ND_ATTN_DKDV_NB, profiles/r4_attention_dkdv_ablation.md):
     the same 32-query steps in the same order as the default kernel, so dQ / dK / dV are bitwise equal."""
     from nanodiloco_amd.ops.attention import key_start, rope_cache
@@ -754,9 +761,11 @@ def test_attention_dkdv_prefetch_depth_bitwise(B, T, nh, nkv, hd, pads, nb, monk
         ops.attention(x, cos, sin, B, T, nh, nkv, hd, kstart=ks).backward(do)
         return x.grad
 
-    monkeypatch.delenv("ND_ATTN_DKDV_NB", raising=False)
-    g0 = grads()
-    monkeypatch.setenv("ND_ATTN_DKDV_NB", nb)
-    g1 = grads()
+    with switches(ND_ATTN_DKDV_NB=None) as state:
+        assert state["ND_ATTN_DKDV_NB"] == "0"  # the default dK/dV kernel
+        g0 = grads()
+    with switches(ND_ATTN_DKDV_NB=nb) as state:
+        assert state["ND_ATTN_DKDV_NB"] == nb
+        g1 = grads()
     assert torch.isfinite(g0.float()).all()
     assert torch.equal(g0, g1)

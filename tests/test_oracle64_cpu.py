@@ -289,3 +289,99 @@ def test_outer_step_oracles_vs_torch_twin(comm, drift):
         assert torch.equal(sh, master32.bfloat16())
         if not drift:
             assert torch.equal(master64, sync64)
+
+
+# ------------------------------------------------------------------------------------------ attention
+ATTN = dict(B=2, T=70, nh=4, nkv=2, hd=16)
+ATTN_MODES = ["none", "kstart", "doc"]
+
+
+def _attn_case(mode, dtype=torch.float64):
+    B, T, nh, nkv, hd = (ATTN[k] for k in ("B", "T", "nh", "nkv", "hd"))
+    raw = torch.randn(B * T, (nh + 2 * nkv) * hd, dtype=torch.float64)
+    raw[T // 2, nh * hd:(nh + 1) * hd] *= 20  # a late key with a large score
+    cos, sin = ref.rope_tables(T, hd, 10000.0)
+    dO = o64.spiked(B * T, nh * hd, "cpu").double()
+    kstart = doc = None
+    if mode == "kstart":
+        kstart = torch.tensor([0, 13], dtype=torch.int32)
+    if mode == "doc":
+        ids = torch.full((B, T), 7)
+        ids[0, 30] = ids[1, 0] = ids[1, 63] = ids[1, 64] = 2
+        doc = ops.doc_bounds(ids, 2)
+    return raw.to(dtype), cos, sin, dO, kstart, doc
+
+
+@pytest.mark.parametrize("mode", ATTN_MODES)
+def test_attention_oracle_matches_reference_autograd(mode):
+    """o64.attention on the rotated rows against ref.attention_block (float64 inputs, autograd) on the raw rows, GQA:
+    the output and, through ``rope_out``, the three gradients with respect to the raw rows, 1e-10 of the tensor's
+    maximum.  Fully masked rows (SDPA gives NaN or 0 for them, the oracle 0) are compared to 0 and take no dO."""
+    B, T, nh, nkv, hd = (ATTN[k] for k in ("B", "T", "nh", "nkv", "hd"))
+    raw, cos, sin, dO, kstart, doc = _attn_case(mode)
+    rot = o64.rope(raw, cos, sin, B, T, nh, nkv, hd)
+    r = o64.attention(rot, B, T, nh, nkv, hd, hd ** -0.5, kstart=kstart, doc_start=doc[0] if doc else None, dO=dO,
+                      rope_out=True, cos=cos, sin=sin, o_saved=None)
+    seen = r["seen"].reshape(-1)
+    assert bool(seen.all()) == (mode != "kstart") and int((~seen).sum()) == (13 if mode == "kstart" else 0)
+    x = raw.clone().requires_grad_(True)
+    o = ref.attention_block(x, cos.double(), sin.double(), B, T, nh, nkv, hd, kstart=kstart, doc_bounds=doc)
+    close(o.detach()[seen], r["o"][seen], 1e-10)
+    assert not bool(r["o"][~seen].any())
+    # the oracle's delta uses o rounded to bf16; autograd's does not: give the oracle the unrounded o to compare
+    r = o64.attention(rot, B, T, nh, nkv, hd, hd ** -0.5, kstart=kstart, doc_start=doc[0] if doc else None, dO=dO,
+                      rope_out=True, cos=cos, sin=sin, o_saved=r["o"])
+    (o[seen] * dO[seen]).sum().backward()
+    nq, nk = nh * hd, nkv * hd
+    g = x.grad.nan_to_num(0.0) if mode == "kstart" else x.grad
+    close(g[:, :nq], r["dq"], 1e-10)
+    close(g[:, nq:nq + nk], r["dk"], 1e-10)
+    close(g[:, nq + nk:], r["dv"], 1e-10)
+    assert torch.equal(r["dqkv"], torch.cat([r["dq"], r["dk"], r["dv"]], 1))
+    lse = torch.logsumexp((rot.view(B, T, -1)[..., :hd] @ rot.view(B, T, -1)[..., nq:nq + hd].transpose(1, 2) * hd ** -0.5)
+                          .masked_fill(~r["mask"][:, 0], float("-inf")), -1)
+    close(r["lse2"][:, 0][r["seen"]], lse[r["seen"]] * o64.LOG2E, 1e-12)
+    assert bool((r["lse2"][:, 0][~r["seen"]] == float("-inf")).all())
+
+
+def test_attention_oracle_masks_and_masked_rows():
+    B, T = 3, 67
+    ks = torch.tensor([0, 65, T], dtype=torch.int32)
+    assert torch.equal(o64.attention_mask(B, T, "cpu", kstart=ks), ref.padded_causal_mask(ks, T))
+    ids = torch.randint(0, 5, (B, T))
+    ds, _ = ops.doc_bounds(ids, 2)
+    assert torch.equal(o64.attention_mask(B, T, "cpu", doc_start=ds), ref.doc_causal_mask(ds, T))
+    t = torch.arange(T)
+    assert torch.equal(o64.attention_mask(1, T, "cpu")[0, 0], t[None, :] <= t[:, None])
+    # an all-pad sequence: everything 0 and finite, lse -inf
+    nh, nkv, hd = 2, 1, 8
+    x = torch.randn(B * T, (nh + 2 * nkv) * hd).bfloat16()
+    dO = torch.randn(B * T, nh * hd).bfloat16()
+    for fn in (o64.attention, o64.attention_twin):
+        r = fn(x, B, T, nh, nkv, hd, 0.3, kstart=ks, dO=dO)
+        assert torch.equal(r["seen"], t[None, :] >= ks[:, None].long())
+        pad = ~r["seen"].reshape(-1)
+        for k in ("o", "dq", "dk", "dv"):
+            assert bool(torch.isfinite(r[k]).all()) and not bool(r[k][pad].any()), k
+        assert not bool(r["delta"].transpose(1, 2).reshape(B * T, nh)[pad].any())
+        assert bool((r["lse2"].transpose(1, 2).reshape(B * T, nh)[pad] == float("-inf")).all())
+        assert bool(torch.isfinite(r["lse2"].transpose(1, 2).reshape(B * T, nh)[~pad]).all())
+
+
+@pytest.mark.parametrize("mode", ATTN_MODES)
+def test_attention_twin_is_a_bf16_operand_model(mode):
+    """The twin's distance from the oracle (the unit of the GPU tests' slack) is non-zero and below 2^-6 of the
+    tensor's maximum, for every output: a sanity bound on the model, not on a kernel."""
+    B, T, nh, nkv, hd = (ATTN[k] for k in ("B", "T", "nh", "nkv", "hd"))
+    raw, cos, sin, dO, kstart, doc = _attn_case(mode)
+    rot = o64.rope(raw, cos, sin, B, T, nh, nkv, hd).bfloat16()
+    kw = dict(kstart=kstart, doc_start=doc[0] if doc else None, dO=dO.bfloat16(), rope_out=True, cos=cos, sin=sin)
+    r = o64.attention(rot, B, T, nh, nkv, hd, hd ** -0.5, **kw)
+    tw = o64.attention_twin(rot, B, T, nh, nkv, hd, hd ** -0.5, **kw)
+    for k in ("o", "dq", "dk", "dv", "lse2", "delta"):
+        a, b = tw[k].double(), r[k]
+        fin = torch.isfinite(b)
+        assert torch.equal(torch.isfinite(a), fin), k
+        d = (a[fin] - b[fin]).abs().max().item()
+        assert 0.0 < d < 2.0 ** -6 * b[fin].abs().max().item(), (k, d, b[fin].abs().max().item())
+    assert tw["lse2"].dtype == torch.float32 and tw["delta"].dtype == torch.float32

@@ -24,6 +24,8 @@ from nanodiloco_amd.ops import _ext
 from nanodiloco_amd.ops import reference as ref
 
 from . import _oracle64 as o64
+from ._switches import switches
+from ._frames import _PATTERN, _ints, assert_frame_intact, framed, framed_flat  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -74,41 +76,6 @@ class torch_twin:
     def __exit__(self, *exc):
         ops.set_backend("hip")
         return False
-
-
-# ------------------------------------------------------------------------------------------ sentinel frames
-def _ints(t):
-    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-_PATTERN = {2: 0x7FC1, 4: 0x7FC12345}  # NaN payloads: a stray read shows as well as a stray write
-
-
-def framed(rows, cols, dtype, pad_r=1, pad_c=16):
-    """A [rows, cols] view in the middle of a larger buffer prefilled with a sentinel bit pattern."""
-    big = torch.empty(rows + 2 * pad_r, cols + 2 * pad_c, dtype=dtype, device=DEV)
-    _ints(big).fill_(_PATTERN[big.element_size()])
-    return big, big[pad_r:pad_r + rows, pad_c:pad_c + cols]
-
-
-def framed_flat(n, dtype, pad=16):
-    big = torch.empty(n + 2 * pad, dtype=dtype, device=DEV)
-    _ints(big).fill_(_PATTERN[big.element_size()])
-    return big, big[pad:pad + n]
-
-
-def assert_frame_intact(big, view=None):
-    """Every element of ``big`` outside ``view`` (None: all of it) still holds the sentinel, bit for bit."""
-    b = _ints(big).clone()
-    off = (view.data_ptr() - big.data_ptr()) // big.element_size() if view is not None else 0
-    if view is None:
-        pass
-    elif big.dim() == 1:
-        b[off:off + view.numel()] = _PATTERN[big.element_size()]
-    else:
-        r0, c0 = off // big.stride(0), off % big.stride(0)
-        b[r0:r0 + view.shape[0], c0:c0 + view.shape[1]] = _PATTERN[big.element_size()]
-    assert bool((b == _PATTERN[big.element_size()]).all()), "a neighbouring element was overwritten"
 
 
 def S():
@@ -468,12 +435,21 @@ def _ce_run(x, tgt, scale, with_rows, loss0=3.0):
 @pytest.mark.parametrize("V", CE_V)
 def test_ce_kernel_alone(V, dt):
     """nd_ce_fwd_bwd on given logits, both sides of the dispatch borders at 8192 and 32768 and V % 8 != 0: every
-    dlogits element, lse_out, row_loss (ignored rows exactly 0) and the atomic loss_sum against float64."""
+    dlogits element, lse_out, row_loss (ignored rows exactly 0) and the atomic loss_sum against float64; bf16 rows
+    that take the packed kernel run once more under ND_CE=r, under the name ce_reg16."""
+    k = _ce_kernel_name(V, dt)
+    _ce_alone(V, dt, k)
+    if k == "ce_bf16":  # ND_CE=r: bf16 rows of 8192 < V <= 32768 take the register kernel instead of the packed one
+        with switches(ND_CE="r") as state:
+            assert state["ND_CE"] == "r"
+            _ce_alone(V, dt, "ce_reg16")
+
+
+def _ce_alone(V, dt, k):
     x, tgt = _ce_inputs(V, dt)
     scale = torch.tensor([0.25 / 15], device=DEV)
     lse64, loss64, dl64 = o64.ce_rows(x, tgt, scale.item())
     lse32, loss32, dl32 = _ce_twin(x.float(), tgt, scale)
-    k = _ce_kernel_name(V, dt)
     dl, lse, rows, loss_sum = _ce_run(x, tgt, scale, True)
     chk(dl, dl64, dl32, k + ".dlogits")
     chk(lse, lse64, lse32, k + ".lse")
