@@ -116,6 +116,11 @@ class ParamStore:
         return min(r[0] for r in rs), max(r[1] for r in rs)
 
     # ------------------------------------------------------------------ state
+    @property
+    def separate_shadow(self) -> Optional[torch.Tensor]:
+        """``shadow`` when it is a buffer of its own that an update must refresh; None when it is the master."""
+        return self.shadow if self.shadow.data_ptr() != self.master.data_ptr() else None
+
     def sync_shadow(self):
         if self.shadow is not self.master:
             self.shadow.copy_(self.master)

@@ -93,6 +93,13 @@ class PendingAllReduce:
         self.flat = flat
         self._done = [False] * len(works)
 
+    @classmethod
+    def finished(cls, flat: torch.Tensor, bucket_bytes: int) -> "PendingAllReduce":
+        """An all-reduce of ``flat`` that completed earlier (its result came back from a checkpoint): the same
+        buckets as :meth:`FlatCommunicator.all_reduce_async`, nothing to wait for."""
+        ranges = plan_buckets(0, flat.numel(), flat.element_size(), bucket_bytes)
+        return cls([None] * len(ranges), ranges, flat)
+
     def wait(self, i: int):
         if not self._done[i]:
             w = self.works[i]

@@ -32,6 +32,7 @@ import torch.distributed as dist
 
 from ..utils.schedule import cosine_with_warmup
 from .comm import FlatCommunicator
+from .transports import Transport
 
 
 def _dist_on() -> bool:
@@ -124,6 +125,7 @@ class ModuleDiloco:
         self._sync_time = 0.0
         self._sync_calls = 0
         self.local_step = 0
+        self.transport = Transport()  # no transport state of its own: the empty answers for a checkpoint
 
     # ------------------------------------------------------------------ reference API
     def __call__(self, *args, **kwargs):

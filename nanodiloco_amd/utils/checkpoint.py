@@ -27,11 +27,14 @@ options, a streaming checkpoint without the flags (and the converse) and ``--ela
 says ``"nanodiloco_streaming_local_weights": true`` (not export-ready, like the pending-step flag).  The final
 checkpoint is written after the flush and carries neither.
 
-With ``--comm-error-feedback`` (quantised transport with residuals, parallel/diloco.py) every rank file carries
+What depends on the outer transport is given and taken by ``Diloco.transport`` (parallel/transports.py:
+``rank_state`` / ``shared_state`` / ``load_state``), under the names this text gives.
+
+With ``--comm-error-feedback`` (quantised transport with residuals) every rank file carries
 ``qef.send`` and ``qef.reduce``, and ``trainer_state.json`` records ``comm_error_feedback: {bits, num_workers, plan}``
 (the bucket plan ``[[x, y, c], ...]`` that ``qef.reduce`` is laid out by).  The residuals are an optimisation state
-that may be dropped (``Diloco.load_error_feedback_state`` has the rules and the cost): a stateless checkpoint
-resumes with the flag on from zero residuals, a checkpoint with residuals resumes without the flag and ignores
+that may be dropped (``QuantisedTransport.load_error_feedback_state`` has the rules and the cost): a stateless
+checkpoint resumes with the flag on from zero residuals, a checkpoint with residuals resumes without the flag and ignores
 them, ``qef.send`` survives int8 <-> int4 and ``--elastic-resume`` (surviving ranks; new workers start at zero),
 ``qef.reduce`` only an unchanged plan and worker count.
 
@@ -107,11 +110,9 @@ def _load_st(path: str) -> Dict[str, torch.Tensor]:
 
 def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_state: Optional[Dict[str, Any]] = None,
                     extra: Optional[Dict[str, Any]] = None):
-    pending = diloco.pending_outer_state()  # overlapped mode: saved as pending, not applied
-    streaming = diloco.streaming_config() if hasattr(diloco, "streaming_config") else None
-    stream_pending = diloco.pending_stream_state() if streaming else None
-    stream_local = bool(streaming) and diloco.streaming_local_weights
-    qef = diloco.error_feedback_state() if hasattr(diloco, "error_feedback_state") else None
+    # a collective still in flight (overlapped step, fragment) is waited for and saved as pending, not applied
+    t_per, t_scal = diloco.transport.rank_state()
+    shared, export_flags = diloco.transport.shared_state()
     if env.inner_dp > 1:
         # two-level mode: each GPU of a worker updates only its shard of the outer momentum
         # (parallel/diloco.py, sharded outer step); gather the worker's full buffer before rank 0
@@ -126,22 +127,9 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
     barrier(env)
     store = model.store
     # per-rank state (every rank)
-    per = {"adamw.exp_avg": diloco.inner_optimizer.exp_avg, "adamw.exp_avg_sq": diloco.inner_optimizer.exp_avg_sq}
-    scal: Dict[str, Any] = {"adamw_step": diloco.inner_optimizer.step_count}
-    if pending is not None:
-        # until the pending step lands, every worker's local weights differ (each carries its own
-        # inner progress since the boundary): model.safetensors holds rank 0's, each rank keeps its own
-        per["outer.delta"] = pending["delta"]
-        per["outer.drift_base"] = pending["drift_base"]
-        per["master"] = store.master
-    if streaming:
-        per["master"] = store.master  # local weights differ per worker until flush_fragments
-        if stream_pending is not None:
-            per["stream.delta"] = stream_pending["delta"]
-            scal["stream_pending_fragment"] = stream_pending["fragment"]
-            scal["stream_apply_step"] = stream_pending["apply_step"]
-    if qef is not None:
-        per["qef.send"], per["qef.reduce"] = qef["send"], qef["reduce"]
+    per = {"adamw.exp_avg": diloco.inner_optimizer.exp_avg, "adamw.exp_avg_sq": diloco.inner_optimizer.exp_avg_sq,
+           **t_per}
+    scal: Dict[str, Any] = {"adamw_step": diloco.inner_optimizer.step_count, **t_scal}
     if data_state:
         for k, v in data_state.items():
             if isinstance(v, torch.Tensor):
@@ -153,10 +141,7 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
         json.dump(scal, f)
     if r == 0:
         cfg_json = model.config.to_hf_json()
-        if pending is not None:  # see the module doc: weights are rank 0's local ones, not the synced model
-            cfg_json["nanodiloco_pending_outer_step"] = True
-        if stream_local:  # rank 0's local weights, fragments at different sync ages: not the synced model either
-            cfg_json["nanodiloco_streaming_local_weights"] = True
+        cfg_json.update(export_flags)  # see the module doc: rank 0's local weights, not the synced model
         with open(os.path.join(ckpt_dir, "config.json"), "w") as f:
             json.dump(cfg_json, f, indent=2)
         _save_st(os.path.join(ckpt_dir, "model.safetensors"), {n: store.master_view(n) for n in store.names})
@@ -166,14 +151,7 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
         state = {"step": step, "local_step": diloco.local_step, "outer_step_count": diloco.outer_step_count,
                  "outer_opt_step": diloco.outer_optimizer.step_count, "scheduler": diloco.scheduler.state_dict(),
                  "world_size": env.world_size, "inner_dp": env.inner_dp, "flat_numel": store.numel,
-                 "pending_outer": pending is not None, **(extra or {})}
-        if streaming:
-            state["streaming"] = {**streaming, "frag_steps": list(diloco.frag_steps),
-                                  "fragment_sync_count": diloco.fragment_sync_count, "local_weights": stream_local,
-                                  "pending_fragment": stream_pending["fragment"] if stream_pending else None,
-                                  "pending_apply_step": stream_pending["apply_step"] if stream_pending else None}
-        if qef is not None:
-            state["comm_error_feedback"] = {k: qef[k] for k in ("bits", "num_workers", "plan")}
+                 **shared, **(extra or {})}
         with open(os.path.join(ckpt_dir, "trainer_state.json"), "w") as f:
             json.dump(state, f, indent=2)
     barrier(env)  # every rank's files are in the staging directory
@@ -199,7 +177,7 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     restarts it where the old workers stopped together (``data_state_rank0``; nothing repeated or skipped);
     the HF loader's contiguous shards cannot be re-cut exactly and the resume refuses; synthetic workers keep
     their own random stream (new ones draw a fresh one).  Error-feedback residuals: surviving ranks keep their
-    ``qef.send``, new workers and every ``qef.reduce`` start at zero (``Diloco.load_error_feedback_state``)."""
+    ``qef.send``, new workers and every ``qef.reduce`` start at zero (``QuantisedTransport.load_error_feedback_state``)."""
     found = find_checkpoint(ckpt_dir)
     if found is None:
         raise FileNotFoundError(f"no complete checkpoint at {ckpt_dir}")
@@ -210,7 +188,7 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     old_world = int(state.get("world_size", env.world_size))
     resized = elastic and old_world != env.world_size
     streamed = state.get("streaming")
-    want = diloco.streaming_config() if hasattr(diloco, "streaming_config") else None
+    want = diloco.transport.shared_state()[0].get("streaming")  # this run's options, as a save would record them
     if streamed and elastic:
         raise ValueError(f"checkpoint {ckpt_dir} was written by a streaming run (per-worker local weights): "
                          f"--elastic-resume is not supported for it")
@@ -250,47 +228,28 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     rfile = os.path.join(ckpt_dir, f"rank{env.rank}.safetensors")
     data_state: Dict[str, Any] = {}
     own = os.path.exists(rfile)
-    qef_send = qef_reduce = None
+    t_per, t_scal = {}, {}  # what the transport restores from: this rank's OWN files
     if not own and resized:  # a worker the checkpoint did not have: rank 0's AdamW state, fresh data stream
         rfile = os.path.join(ckpt_dir, "rank0.safetensors")
     elif not own and "world_size" in state:
         raise FileNotFoundError(f"{rfile} missing: the checkpoint is incomplete for rank {env.rank}")
     if os.path.exists(rfile):
         per = _load_st(rfile)
-        if state.get("pending_outer"):
-            store.master.copy_(per["master"].to(store.master.device))
-            diloco.restore_pending_outer(per["outer.delta"].to(diloco.delta.device),
-                                         per["outer.drift_base"].to(diloco.delta.device))
-        if streamed:
-            store.master.copy_(per["master"].to(store.master.device))
-            diloco.frag_steps = [int(x) for x in streamed["frag_steps"]]
-            diloco.fragment_sync_count = int(streamed.get("fragment_sync_count", 0))
-            diloco._flushed = not streamed.get("local_weights", True)
-            if "stream.delta" in per:
-                with open(rfile[:-len(".safetensors")] + ".json") as f:
-                    sj = json.load(f)
-                diloco.restore_pending_stream(per["stream.delta"].to(diloco.delta.device),
-                                              int(sj["stream_pending_fragment"]), int(sj["stream_apply_step"]))
         diloco.inner_optimizer.exp_avg.copy_(per["adamw.exp_avg"])
         diloco.inner_optimizer.exp_avg_sq.copy_(per["adamw.exp_avg_sq"])
         with open(rfile[:-len(".safetensors")] + ".json") as f:
             scal = json.load(f)
         diloco.inner_optimizer.step_count = int(scal["adamw_step"])
         if own:
-            qef_send, qef_reduce = per.get("qef.send"), per.get("qef.reduce")
+            t_per, t_scal = per, scal
             for k, v in per.items():
                 if k.startswith("data."):
                     data_state[k[5:]] = v
             for k, v in scal.items():
                 if k.startswith("data."):
                     data_state[k[5:]] = v
-    if hasattr(diloco, "load_error_feedback_state"):
-        saved = state.get("comm_error_feedback")
-        had = saved is not None or qef_send is not None
-        if had or diloco.error_feedback:
-            for line in diloco.load_error_feedback_state(qef_send, qef_reduce, saved):
-                if env.rank == 0 or (diloco.error_feedback and had and qef_send is None):
-                    print(f"[resume] rank {env.rank}: {line}", flush=True)
+    for line in diloco.transport.load_state(t_per, t_scal, state):
+        print(f"[resume] rank {env.rank}: {line}", flush=True)
     state["data_state"] = data_state
     if resized:
         # the data sources whose stream is global (memmap) restart every worker -- survivors and new ones --

@@ -113,7 +113,8 @@ def main():
         bound = (amax / qmax / 2 + amax / qmax / 2) * LR * (1 + MU)
         err = (m_1 - m_f).abs().max().item()
         check(0 < err <= bound, f"{comm}: |quantised - fp32 transport| = {err:.3e} <= {bound:.3e}")
-        check(dl_1.bytes_per_outer_step == sum(bk.send.numel() for bk in dl_1._qplan) > 0, f"{comm}: wire bytes reported")
+        check(dl_1.bytes_per_outer_step == sum(bk.send.numel() for bk in dl_1.transport._qplan) > 0,
+              f"{comm}: wire bytes reported")
     if not CPU:
         from nanodiloco_amd.parallel import rccl
         for c in list(rccl._COMMS.values()):  # a clean destroy: the drain and ncclCommDestroy report no error

@@ -52,8 +52,8 @@ def main():
         bits = int(comm[3:])
         m0, d0 = make(env, comm, False)
         m1, d1 = make(env, comm, True)
-        check(d1.qef_send.numel() == n and d1.qef_reduce.numel() == sum(bk.c for bk in d1._qplan)
-              and len(d1._qplan) > 1, f"{comm}: residual buffers cover the span and one chunk per bucket")
+        check(d1.qef_send.numel() == n and d1.qef_reduce.numel() == sum(bk.c for bk in d1.transport._qplan)
+              and len(d1.transport._qplan) > 1, f"{comm}: residual buffers cover the span and one chunk per bucket")
         for m, d in ((m0, d0), (m1, d1)):
             m.store.master.add_(drifts[0])
             d.outer_step()
@@ -70,7 +70,7 @@ def main():
         shadow = st.shadow.clone() if st.shadow.data_ptr() != st.master.data_ptr() else None
         e1, e2 = d1.qef_send.clone(), d1.qef_reduce.clone()
         off = 0
-        for bk in d1._qplan:
+        for bk in d1.transport._qplan:
             pb = qcomm.chunk_bytes(bk.c, bits)
             send, red = (torch.zeros(pb, dtype=torch.uint8, device=dev) for _ in range(2))
             ops.pseudograd_q_ef(sync[bk.x:bk.y], master[bk.x:bk.y], e1[bk.x:bk.y], send, 1, bk.c, bits)

@@ -80,14 +80,14 @@ def test_checkpoint_keeps_overlapped_outer_step_pending(tmp_path):
                          overlap=True)
     m, d = mk(0)
     _train(m, d, 4, torch.Generator().manual_seed(0))
-    assert d._pending is not None
+    assert d.transport._pending is not None
     save_checkpoint(str(tmp_path), m, d, DistEnv(), step=4)
     assert json.load(open(tmp_path / "trainer_state.json"))["pending_outer"] is True
-    assert d._pending is not None  # saving did not apply it
+    assert d.transport._pending is not None  # saving did not apply it
     _train(m, d, 4, torch.Generator().manual_seed(1))
     m2, d2 = mk(99)
     load_checkpoint(str(tmp_path), m2, d2, DistEnv())
-    assert d2._pending is not None
+    assert d2.transport._pending is not None
     _train(m2, d2, 4, torch.Generator().manual_seed(1))
     d.finalize(), d2.finalize()
     assert torch.equal(m.store.master, m2.store.master) and torch.equal(d.sync, d2.sync)

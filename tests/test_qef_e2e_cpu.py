@@ -123,12 +123,13 @@ def _several_buckets(rank, world):
     nb = -(-st.numel // (4 * unit))
     last = st.numel - (nb - 1) * 4 * unit
     assert dl.buckets_per_outer_step == nb > 3 and 0 < last < 4 * unit
-    assert [bk.c for bk in dl._qplan] == [4 * 256] * (nb - 1) + [last // 3]
-    assert dl.bytes_per_outer_step == sum(3 * (bk.c + bk.c // 256 * 4) for bk in dl._qplan)
+    assert [bk.c for bk in dl.transport._qplan] == [4 * 256] * (nb - 1) + [last // 3]
+    assert dl.bytes_per_outer_step == sum(3 * (bk.c + bk.c // 256 * 4) for bk in dl.transport._qplan)
     assert dl.qef_send.numel() == b - a == st.numel
-    assert dl.qef_reduce.numel() == sum(bk.c for bk in dl._qplan) == (nb - 1) * 4 * 256 + last // 3
-    assert [v.numel() for v in dl._qef_views] == [bk.c for bk in dl._qplan]
-    assert all(v.data_ptr() == dl.qef_reduce.data_ptr() + 4 * 4 * 256 * i for i, v in enumerate(dl._qef_views))
+    assert dl.qef_reduce.numel() == sum(bk.c for bk in dl.transport._qplan) == (nb - 1) * 4 * 256 + last // 3
+    assert [v.numel() for v in dl.transport._qef_views] == [bk.c for bk in dl.transport._qplan]
+    assert all(v.data_ptr() == dl.qef_reduce.data_ptr() + 4 * 4 * 256 * i
+               for i, v in enumerate(dl.transport._qef_views))
     _, m2, dl2 = _mk(torch.float32, env=env, ef=False)
     amax = SIGMA * 6
     resid = 3 * amax / 127 / 2 + 3 * amax / 127 / 2 + STEPS * (3 + 1) * 2.0 ** -23 * (2 * 3 * amax)
@@ -167,7 +168,7 @@ def _step(m, dl, s):
 
 def _checkpoints(rank, world, tmp):
     env, m, dl = _mk("int8", bucket_mb=BUCKET)
-    assert len(dl._qplan) > 2
+    assert len(dl.transport._qplan) > 2
     _step(m, dl, 0)
     save_checkpoint(os.path.join(tmp, "ef"), m, dl, env, 4)
     send1, red1 = dl.qef_send.clone(), dl.qef_reduce.clone()
@@ -175,7 +176,7 @@ def _checkpoints(rank, world, tmp):
     _step(m, dl, 1)
     with open(os.path.join(tmp, "ef", "trainer_state.json")) as f:
         meta = json.load(f)["comm_error_feedback"]
-    assert meta == {"bits": 8, "num_workers": 2, "plan": [[bk.x, bk.y, bk.c] for bk in dl._qplan]}
+    assert meta == {"bits": 8, "num_workers": 2, "plan": [[bk.x, bk.y, bk.c] for bk in dl.transport._qplan]}
     # save after step 1, load into a fresh instance, step 2: the uninterrupted run, bitwise
     _, m2, dl2 = _mk("int8", env=env, bucket_mb=BUCKET, seed=8)
     load_checkpoint(os.path.join(tmp, "ef"), m2, dl2, env)
@@ -206,7 +207,7 @@ def _checkpoints(rank, world, tmp):
     assert bool(torch.isfinite(m5.store.master).all()) and not torch.equal(m5.store.master, m.store.master)
     # int8 -> int4: qef.send is per element and stays; qef.reduce follows the plan, which differs: zero
     _, m6, dl6 = _mk("int4", env=env, bucket_mb=BUCKET, seed=11)
-    assert [[bk.x, bk.y, bk.c] for bk in dl6._qplan] != meta["plan"]
+    assert [[bk.x, bk.y, bk.c] for bk in dl6.transport._qplan] != meta["plan"]
     dl6.qef_reduce.fill_(1.0)
     load_checkpoint(os.path.join(tmp, "ef"), m6, dl6, env)
     assert torch.equal(dl6.qef_send, send1) and not bool(dl6.qef_reduce.any())
