@@ -215,34 +215,6 @@ __device__ __forceinline__ float pair_sum32(float x) {
 // here are <= 0 (scores minus a running max / LSE); results below 2^-126 flush to 0, harmless for P.
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// Softmax-arithmetic experiment switches, compiled into A/B side libraries only
-// (`build.py --rev ... --extra-flags -DND_ATTN_X=<bits>`); the product library is built with 0.
-//   1  s_setprio 1 around the S (/ dP) MFMA chains, the critical path of every kernel
-//   2  packed f32 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) for the score transform, the row sum and
-//      the dS products -- bitwise the scalar forms (same per-element ops, same summation order)
-//   4  forward: 4 of every 32 exp2s by round-to-nearest range reduction + a degree-6 polynomial on the
-//      FMA pipe instead of v_exp_f32
-//   8  s_setprio 1 around the P V (fwd) / dQ (dq) / dV dK (dkdv) MFMA chains
-//  16  s_setprio 1 around the softmax / dS VALU block instead (the critical path between the two chains)
-//  32  forward: 3 waves / SIMD (launch bound 3, 168 VGPRs, no spill) instead of 4
-//  64  dK/dV: 64-query tiles at 3 waves / SIMD (launch bound 3: 33 KiB of LDS, <= 168 VGPRs) instead of
-//      128-query tiles at 2
-// 128  dK/dV (128-query tiles): the next tile's LDS-DMA pieces spread over the first three 32-query steps (Q, then
-//      dO, then the row statistics) instead of all issued after the tile's barrier
-// 256  forward: the two 32-key S chains interleaved MFMA by MFMA instead of one after the other
-// 512  the round-5 wait placement (no settle() of the prologue fragment loads; A/B of the fix only)
-#ifndef ND_ATTN_X
-#define ND_ATTN_X 0
-#endif
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2v pk_fma(f2v a, f2v b, f2v c) { return __builtin_elementwise_fma(a, b, c); }
-template <int BIT>
-__device__ __forceinline__ void xprio(int p) {
-  if constexpr ((ND_ATTN_X & BIT) != 0) {
-    if (p) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-  }
-}
 // In-kernel segment stamps (diagnostic build only: -DND_ATTN_STAMP, never the product library; guide
 // cdna_hip_programming.md §7 "In-kernel stamps"): s_memtime + lgkmcnt(0) as one statement between scheduling
 // barriers; each segment's cycles are summed in scalar registers and every wave's lane 0 writes its sums to a
@@ -290,26 +262,8 @@ ND_API int nd_attn_stamp_buffer(void* p) {
 // one vmcnt(0) here instead.
 template <int N>
 __device__ __forceinline__ void settle(const bf16x8 (&f)[N]) {
-  if constexpr ((ND_ATTN_X & 512) == 0) {
 #pragma unroll
-    for (int t = 0; t < N; ++t) asm volatile("" ::"v"(f[t]));
-  }
-}
-
-// 2^x for x <= 0 without the transcendental unit: x = j + f, j = rint(x) by the 1.5 * 2^23 shifter,
-// f in [-0.5, 0.5], 2^f by its degree-6 Taylor polynomial (relative error < 2e-7), 2^j into the exponent.
-__device__ __forceinline__ float pexp2(float x) {
-  const float xc = fmaxf(x, -126.f);
-  const float t = xc + 12582912.f;
-  const float f = xc - (t - 12582912.f);
-  float p = fmaf(1.5403530e-4f, f, 1.3333558e-3f);
-  p = fmaf(p, f, 9.6181291e-3f);
-  p = fmaf(p, f, 5.5504109e-2f);
-  p = fmaf(p, f, 2.4022651e-1f);
-  p = fmaf(p, f, 6.9314718e-1f);
-  p = fmaf(p, f, 1.f);
-  const float r = __int_as_float(__float_as_int(p) + ((__float_as_int(t) - 0x4B400000) << 23));
-  return x < -126.f ? 0.f : r;
+  for (int t = 0; t < N; ++t) asm volatile("" ::"v"(f[t]));
 }
 
 // Store a [HD x 32] transposed accumulator (rows = head dim in registers, col = row index on the
@@ -460,7 +414,7 @@ __device__ __forceinline__ uint32_t bit_range(int lo, int hi) {
   return (uint32_t)((1ull << u) - 1) & (uint32_t)(~0ull << l);
 }
 template <int HD, bool ROPE, bool DMA = false, int MASK = MASK_NONE, int ABL = 0, int NW = 4>  // DMA: LDS-DMA K/V staging (!ROPE, T % 64 == 0)
-__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && !(ND_ATTN_X & 32)) ? 4 : 3)) attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 4 : 3)) attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
                                                           float* __restrict__ LSE, int B, int nh, int nkv, int T,
                                                           int64_t ld, int64_t ldo, float scale,
@@ -581,16 +535,6 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
 #pragma unroll
         for (int t = 0; t < NT; ++t) ka[kt][t] = row_frag<HD>(Kt, kt * 32 + c32, t, h);
       f32x16 s[2];
-      xprio<1>(1);
-      if constexpr ((ND_ATTN_X & 256) != 0 && !(ABL & 16)) {
-        // the two 32-key chains interleaved: two MFMAs between a K-fragment read and its use, not one
-        s[0] = f32x16{};
-        s[1] = f32x16{};
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt) s[kt] = mfma32(ka[kt][t], qf[t], s[kt]);
-      } else {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         s[kt] = f32x16{};
@@ -600,8 +544,6 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
           else s[kt] = mfma32(ka[kt][t], qf[t], s[kt]);
         }
       }
-      }
-      xprio<1>(0);
       ND_STAMP(stp.mark(3);)
       if constexpr (ABL & 4) {
 #pragma unroll
@@ -617,7 +559,6 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
           }
         return;
       }
-      xprio<16>(1);
       float mx;
       if constexpr (ABL & 32) {
         // variant 32: one compare + select per score against a per-lane limit (T % 64 == 0 here: no
@@ -684,48 +625,22 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
       m = mnew;
       float rs4[4] = {0.f, 0.f, 0.f, 0.f};  // variant 32: four independent partial sums
       float rs = 0.f;
-      if constexpr ((ND_ATTN_X & 2) != 0 && (ABL & 32) != 0) {
-        // packed: rsp[0] = (rs4[0], rs4[1]), rsp[1] = (rs4[2], rs4[3]) -- the scalar order exactly
-        f2v rsp[2] = {f2v{0.f, 0.f}, f2v{0.f, 0.f}};
-        const f2v c2 = {c, c}, nm2 = {-mref, -mref};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            f2v x = pk_fma(f2v{s[kt][r], s[kt][r + 1]}, c2, nm2);
-            if constexpr ((ND_ATTN_X & 4) != 0) {
-              x.x = fexp2(x.x);
-              x.y = (r & 7) == 6 ? pexp2(x.y) : fexp2(x.y);
-            } else {
-              x.x = fexp2(x.x);
-              x.y = fexp2(x.y);
-            }
-            s[kt][r] = x.x;
-            s[kt][r + 1] = x.y;
-            rsp[(r >> 1) & 1] += x;
-          }
-        rs = (rsp[0].x + rsp[0].y) + (rsp[1].x + rsp[1].y);
-      } else {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float xx = fmaf(s[kt][r], c, -mref);
-          const float p = ((ND_ATTN_X & 4) != 0 && (r & 7) == 7) ? pexp2(xx) : fexp2(xx);
+          const float p = fexp2(fmaf(s[kt][r], c, -mref));
           s[kt][r] = p;
           if constexpr (ABL & 32) rs4[r & 3] += p;
           else rs += p;
         }
       if constexpr (ABL & 32) rs = (rs4[0] + rs4[1]) + (rs4[2] + rs4[3]);
-      }
       l = l * alpha + rs;
       if (__any(alpha != 1.f)) {
 #pragma unroll
         for (int o = 0; o < NO; ++o) oacc[o] *= alpha;
       }
-      xprio<16>(0);
       ND_STAMP(stp.mark(4);)
-      xprio<8>(1);
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -737,7 +652,6 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && 
             else oacc[o] = mfma32(tr_frag<HD>(Vt, kt * 32 + 16 * sidx, o * 32, g, i16), pf, oacc[o]);
           }
         }
-      xprio<8>(0);
       ND_STAMP(stp.mark(5);)
     }
     if constexpr (!DMA) {
@@ -815,11 +729,8 @@ __global__ void __launch_bounds__(256) attn_bwd_pre_kernel(const bf16_t* __restr
 // half of O, dots, and one lane^32 exchange gives delta = rowsum(dO * O); the kernel then writes
 // -delta and -LSE/c (the seeds of the dK/dV kernel, which therefore runs after this one).
 // NW: waves per workgroup (8 = 256-query blocks, LDS-DMA only; see attn_fwd_kernel)
-#ifndef ND_ATTN_DQ_OCC
-#define ND_ATTN_DQ_OCC 2  // waves / SIMD the head_dim-64 dQ kernel is compiled for (A/B)
-#endif
 template <int HD, bool ROPE, bool ROPE_OUT, bool DMA = false, bool PRE = false, int MASK = MASK_NONE, int NW = 4>  // DMA: LDS-DMA K/V staging; MASK: see attn_fwd_kernel
-__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_DQ_OCC : 2)) attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                              const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
                                                              const float* __restrict__ LSE, const float* __restrict__ DELTA,
                                                              bf16_t* __restrict__ dQ, int B, int nh, int nkv, int T,
@@ -965,31 +876,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
           for (int o = 0; o < NO; ++o) tk[sidx][o] = tr_frag<HD>(Kt, kt * 32 + 16 * sidx, o * 32, g, i16);
         ND_STAMP(stp.mark(3);)
         f32x16 s = f32x16{}, dp = f32x16{};
-        xprio<1>(1);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           s = mfma32(ka[t], qf[t], s);
           dp = mfma32(va[t], dof[t], dp);
         }
-        xprio<1>(0);
         ND_STAMP(stp.mark(4);)
-        xprio<16>(1);
         if (!diag) {
-          if constexpr ((ND_ATTN_X & 2) != 0) {
-            const f2v c2 = {c, c}, nl2 = {-lse, -lse}, nd2 = {-dlt, -dlt};
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              f2v x = pk_fma(f2v{s[r], s[r + 1]}, c2, nl2);
-              x.x = fexp2(x.x);
-              x.y = fexp2(x.y);
-              const f2v y = x * (f2v{dp[r], dp[r + 1]} + nd2);
-              dp[r] = y.x;
-              dp[r + 1] = y.y;
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dp[r] = fexp2(fmaf(s[r], c, -lse)) * (dp[r] - dlt);
-          }
+          for (int r = 0; r < 16; ++r) dp[r] = fexp2(fmaf(s[r], c, -lse)) * (dp[r] - dlt);
         } else if constexpr (DOC) {
           const int ds = dw.start_of(q0w, c32);
           const int koff = k0 + kt * 32 + 4 * h - ds;
@@ -1007,16 +902,13 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : HD == 64 ? ND_ATTN_D
             dp[r] = p * (dp[r] - dlt);
           }
         }
-        xprio<16>(0);
         ND_STAMP(stp.mark(5);)
-        xprio<8>(1);
 #pragma unroll
         for (int sidx = 0; sidx < 2; ++sidx) {
           const bf16x8 dsf = pack_frag(dp, sidx);
 #pragma unroll
           for (int o = 0; o < NO; ++o) dq[o] = mfma32(tk[sidx][o], dsf, dq[o]);
         }
-        xprio<8>(0);
         ND_STAMP(stp.mark(6);)
       }
     }
@@ -1206,12 +1098,9 @@ __global__ void __launch_bounds__(256, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_kernel
 // forward's 32) are compiled only into a -DND_ABLATION build (`python -m nanodiloco_amd.csrc.build
 // --ablation` -> _lib/alt/libnd_kernels_ablation.so), so a stray ND_ATTN_*ABL variable cannot change
 // what a training job computes.
-#ifndef ND_ATTN_DKDV_ORDER_DEFAULT
-#define ND_ATTN_DKDV_ORDER_DEFAULT 0
-#endif
 struct AttnEnv {
   int order = 1;        // ND_ATTN_ORDER: grid order (see attn_fwd_kernel)
-  int dkdv_order = ND_ATTN_DKDV_ORDER_DEFAULT;   // ND_ATTN_DKDV_ORDER: bit 0 group the key blocks of one (batch, kv head), bit 1 descending query walk
+  int dkdv_order = 0;   // ND_ATTN_DKDV_ORDER: bit 0 group the key blocks of one (batch, kv head), bit 1 descending query walk
   float thr = 8.f;      // ND_ATTN_THR: deferred-max threshold (log2 units; 0 = move the max on every increase)
   bool fwd_reg = false; // ND_ATTN_FWD=r: register-staged forward
   int fwd_var = 32;     // ND_ATTN_ABL: 32 (cheaper mask / v_max3 tree, 1.007-1.024x) or 0 (plain)
@@ -1414,7 +1303,7 @@ __global__ void __launch_bounds__(256) attn_neg_stats_kernel(const float* __rest
 // NB: Q / dO / statistics buffers in LDS; tile it + NB - 1 is in flight while tile it is computed
 // MASK_DOC: KS = doc_end [B, T]; the query-tile walk ends with the document of the block's last key
 template <int HD, bool ROPE_OUT, int BQ = 64, int MASK = MASK_NONE, int NW = 4, int ABL = 0, int NB = 2>
-__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 64 && (ND_ATTN_X & 64)) ? 3 : 2)) attn_bwd_dkdv_dma_kernel(
+__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dma_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ NL, const float* __restrict__ ND, bf16_t* __restrict__ dK,
     bf16_t* __restrict__ dV, int B, int nh, int nkv, int T, int64_t ld, int64_t ldo, float scale,
@@ -1506,8 +1395,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
     return desc ? ntq - 1 - r : r;
   };
   ND_STAMP(Stamps stp; stp.start();)
-  // part: 7 = everything; 1 = Q pieces, 2 = dO pieces, 4 = row statistics (ND_ATTN_X & 128 spreads them)
-  auto issue = [&](int it, int part = 7) {
+  auto issue = [&](int it) {
     const int head = kvh * rep + it / ntq;
     const int q0 = qstart + qtile(it) * BQ;
     const int buf = it % NB;
@@ -1517,15 +1405,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
     for (int i = 0; i < IPW; ++i) {
       const uint32_t off = (uint32_t)(buf * BQ * HD * 2 + (wu + NW * i) * 1024);
       if constexpr (DOC) {
-        if (part & 1) gdma(sq + (int64_t)(i * NW * RPI) * ld, vq[0], qs_a + off);
-        if (part & 2) gdma(sd + (int64_t)(i * NW * RPI) * ldo, vd[0], do_a + off);
+        gdma(sq + (int64_t)(i * NW * RPI) * ld, vq[0], qs_a + off);
+        gdma(sd + (int64_t)(i * NW * RPI) * ldo, vd[0], do_a + off);
       } else {
-        if (part & 1) gdma(sq, vq[i], qs_a + off);
-        if (part & 2) gdma(sd, vd[i], do_a + off);
+        gdma(sq, vq[i], qs_a + off);
+        gdma(sd, vd[i], do_a + off);
       }
     }
     ND_STAMP(stp.mark(9);)
-    if ((part & 4) && wu < BQ / 64) {  // one 64-float wave-instruction per 64 rows
+    if (wu < BQ / 64) {  // one 64-float wave-instruction per 64 rows
       const int64_t rs = ((int64_t)b * nh + head) * T + q0 + wu * 64;
       adma_b32(NL + rs, (uint32_t)(lane * 4), ls_a + (buf * BQ + wu * 64) * 4);
       adma_b32(ND + rs, (uint32_t)(lane * 4), ds_a + (buf * BQ + wu * 64) * 4);
@@ -1537,7 +1425,6 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
     if (j < nit) issue(j);
   bf16x8 qa[NT], da[NT], tdo[2][NO], tq[2][NO];
   bool first = true;
-  constexpr bool SPREAD = (ND_ATTN_X & 128) != 0 && BQ == 128 && NB == 2;
   for (int it = 0; it < nit; ++it) {
     ND_STAMP(stp.mark(7);)
     if constexpr (!(ABL & 1)) {  // this wave's part of tile it has landed; tiles it+1 .. it+NB-2 may stay in flight
@@ -1556,7 +1443,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
     ND_STAMP(stp.mark(0);)
     if constexpr (!(ABL & 2)) __syncthreads();        // everyone's; and tile it-1's buffer is free
     ND_STAMP(stp.mark(1);)
-    if constexpr (!(ABL & 1) && !SPREAD) if (it + NB - 1 < nit) issue(it + NB - 1);
+    if constexpr (!(ABL & 1)) if (it + NB - 1 < nit) issue(it + NB - 1);
     const int q0 = qstart + qtile(it) * BQ;
     const int buf = it % NB;
     const bf16_t* Qt = Qs + buf * (BQ * HD);
@@ -1565,8 +1452,6 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
     const float* dt = del_s + buf * BQ;
 #pragma unroll
     for (int qs = 0; qs < BQ / 32; ++qs) {
-      if constexpr (SPREAD && !(ABL & 1))
-        if (qs < 3 && it + 1 < nit) issue(it + 1, 1 << qs);  // before the skip test: every wave issues its pieces
       const int qsub = q0 + qs * 32;
       if (kw0 > qsub + 31 || kw0 >= T) continue;  // wave-uniform: no query >= any of our keys
       if (DOC && qsub >= dew1) continue;          // wave-uniform: every query past our last key's document
@@ -1574,10 +1459,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
       // for dV / dK) so their latency hides behind the MFMA chains and the softmax VALU instead of
       // being exposed one s_waitcnt at a time.
       ND_STAMP(stp.mark(7);)
-      // ND_ATTN_X & 64 (A/B): fragments read just before their MFMAs instead, in three phases the scheduler
-      // may not merge -- the register budget of 3 waves / SIMD; the partner waves cover the read latency
-      constexpr bool JIT = (ND_ATTN_X & 64) != 0 && HD == 64 && BQ == 64;
-      const bool rd = (!(ABL & 32) || first) && !JIT;
+      const bool rd = !(ABL & 32) || first;
       first = false;
       if (rd) {
 #pragma unroll
@@ -1605,47 +1487,25 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
           }
       }
       ND_STAMP(stp.mark(2);)
-      xprio<1>(1);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         if constexpr ((ABL & 8) != 0) {
           s[t] += (float)qa[t][0];
           dp[t] += (float)da[t][0];
-        } else if constexpr (JIT) {
-          s = mfma32(row_frag<HD>(Qt, qs * 32 + c32, t, h), kf[t], s);
-          dp = mfma32(row_frag<HD>(dOt, qs * 32 + c32, t, h), vf[t], dp);
         } else {
           s = mfma32(qa[t], kf[t], s);
           dp = mfma32(da[t], vf[t], dp);
         }
       }
-      if constexpr (JIT) __builtin_amdgcn_sched_barrier(0);
-      xprio<1>(0);
       ND_STAMP(stp.mark(3);)
-      xprio<16>(1);
       const bool diag = (kw0 + 31 > qsub) || (qsub + 31 >= T) || (key >= T) || (PAD && kw0 < ks) || (DOC && qsub + 31 >= dew0);
       if constexpr ((ABL & 4) != 0) {
       } else if (!diag) {
-        if constexpr ((ND_ATTN_X & 2) != 0) {
-          const f2v c2 = {c, c};
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            f2v x = f2v{s[r], s[r + 1]} * c2;
-            x.x = fexp2(x.x);
-            x.y = fexp2(x.y);
-            const f2v y = x * f2v{dp[r], dp[r + 1]};
-            s[r] = x.x;
-            s[r + 1] = x.y;
-            dp[r] = y.x;
-            dp[r + 1] = y.y;
-          }
-        } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = fexp2(s[r] * c);
           s[r] = p;
           dp[r] = p * dp[r];
-        }
         }
       } else if constexpr (DOC) {
         // key <= qq < doc_end (every query of a tile and every key of a running wave is < T)
@@ -1665,10 +1525,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
           dp[r] = p * dp[r];
         }
       }
-      xprio<16>(0);
-      if constexpr (JIT) __builtin_amdgcn_sched_barrier(0);
       ND_STAMP(stp.mark(4);)
-      xprio<8>(1);
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) {
         const bf16x8 pf = pack_frag(s, sidx);
@@ -1678,16 +1535,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && BQ == 6
           if constexpr ((ABL & 16) != 0) {
             dv[o][sidx] += (float)pf[o] + (float)tdo[sidx][o][0];
             dk[o][sidx] += (float)dsf[o] + (float)tq[sidx][o][0];
-          } else if constexpr (JIT) {
-            dv[o] = mfma32(tr_frag<HD>(dOt, qs * 32 + 16 * sidx, o * 32, g, i16), pf, dv[o]);
-            dk[o] = mfma32(tr_frag<HD>(Qt, qs * 32 + 16 * sidx, o * 32, g, i16), dsf, dk[o]);
           } else {
             dv[o] = mfma32(tdo[sidx][o], pf, dv[o]);
             dk[o] = mfma32(tq[sidx][o], dsf, dk[o]);
           }
         }
       }
-      xprio<8>(0);
       ND_STAMP(stp.mark(5);)
     }
   }
@@ -1812,7 +1665,7 @@ static int bwd_fused_launch(const void* q, const void* k, const void* v, const v
     else if (nbv == 3) ND_DN(3);
     else ND_DN(4);
 #undef ND_DN
-  } else if (T % 128 == 0 && !(ND_ATTN_X & 64)) {
+  } else if (T % 128 == 0) {
     switch (g_attn.dkdv_abl) {  // always 0 outside an ND_ABLATION build
 #ifdef ND_ABLATION
 #define ND_DA(X) case X: hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<HD, ROPE_OUT, 128, PAD, 4, X>), dim3(nb * B * nkv), \

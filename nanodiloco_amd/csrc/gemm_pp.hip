@@ -75,10 +75,9 @@ constexpr uint32_t BUF_B = 4 * HALF_B;     // bytes of one K-tile buffer (64 KiB
 constexpr int LGKM0 = 0xC07F;              // s_waitcnt lgkmcnt(0), vmcnt / expcnt at their maxima
 
 enum : int { PP_STORE = 0, PP_ROPE = 1, PP_SWIGLU = 2, PP_DSWIGLU = 3 };
-#ifndef ND_MLP_COEF_DEFAULT
-#define ND_MLP_COEF_DEFAULT 1  // saved-tensor form of the fused SwiGLU pair (g_mlp_coef below): the coefficient form
-                               // (down dgrad + SwiGLU backward 1.046x, step +0.2 %: profiles/r6_mlp_coef_ab.md)
-#endif
+// saved-tensor form of the fused SwiGLU pair (g_mlp_coef below): the coefficient form
+// (down dgrad + SwiGLU backward 1.046x, step +0.2 %: profiles/r6_mlp_coef_ab.md)
+constexpr bool kMlpCoefDefault = true;
 
 struct PPEpi {
   const float* cosT;  // PP_ROPE: fp32 [T, hd] tables (HF cat(freqs, freqs) layout)
@@ -99,28 +98,15 @@ struct PPEpi {
 
 // stores per wave per tile epilogue (counted by the vmcnt waits that follow it)
 template <int EPI> struct NStores { static constexpr int v = EPI == PP_SWIGLU ? 24 : EPI == PP_DSWIGLU ? 32 : 16; };
-#ifndef DSW_PF
-#define DSW_PF 6  // PP_DSWIGLU epilogue: gate / up load steps in flight
-#endif
+constexpr int kDswPf = 6;  // PP_DSWIGLU epilogue: gate / up load steps in flight
 
-// accumulator pinned to AGPRs (tied operand): the chain on one accumulator needs no wait states;
-// compiler code reading the result waits for drain()
-#ifndef ND_PP_ASM_MFMA
 __device__ __forceinline__ void mma(const bf16x8& a, const bf16x8& b, f32x4& c) {
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bfv8, a), __builtin_bit_cast(bfv8, b), c, 0, 0, 0);
 }
+// first k-step of a tile: zero accumulator input (no per-tile zeroing)
 __device__ __forceinline__ void mma0(const bf16x8& a, const bf16x8& b, f32x4& c) {
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bfv8, a), __builtin_bit_cast(bfv8, b), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 }
-#else
-__device__ __forceinline__ void mma(const bf16x8& a, const bf16x8& b, f32x4& c) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-// first k-step of a tile: zero accumulator input (no per-tile AGPR zeroing)
-__device__ __forceinline__ void mma0(const bf16x8& a, const bf16x8& b, f32x4& c) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-}
-#endif
 // fp8 operands (F8 1: A e4m3, B e4m3; 2: A e5m2, B e4m3): one 16x16x128 MFMA on the two 16-B halves of
 // each fragment (the lane's 32 K bytes), unit E8M0 block scales (`one` = 0x7F7F7F7F).  The MFMA's first
 // source is B (cbsz = B's format), its second A (blgp = A's format).
@@ -342,7 +328,7 @@ __device__ __forceinline__ void pp_epilogue(const f32x4 (&acc)[8][4], bf16_t* __
       // the 16 (row block, column pair) steps read gate / up from HBM: their loads run PF steps ahead
       // (2 x PF x 4 VGPRs, taken from the next K-tile's fragment registers, free here) instead of one
       // -- one exposed HBM round trip per tile instead of per step
-      constexpr int PF = Q != 0 ? 4 : DSW_PF;  // the fp8-output form needs the registers
+      constexpr int PF = Q != 0 ? 4 : kDswPf;  // the fp8-output form needs the registers
       u32x4 gq[PF], uq[PF];
       auto gu_off = [&](int st, int half) -> uint32_t {
         const int a = st >> 1, bp = st & 1;
@@ -580,20 +566,10 @@ __global__ void __launch_bounds__(512, 1) gemm_pp_kernel(const bf16_t* __restric
       const bool full = EPI == PP_SWIGLU ? p.n0 + 128 <= N : p.n0 + 128 * h + 128 <= N;
       if (!(ABL & 1024) && full) {
         const char* base = B + ((int64_t)(p.n0 + (EPI == PP_SWIGLU ? 64 : 128) * h) * ldb + (int64_t)p.kt * TKE) * ES;
-        if constexpr (ND_DMA_BURST) {
-          gdma4<4096>(base, voff[0], voff[1], voff[2], voff[3], dst + (uint32_t)h * HALF_B);
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) gdma(base, voff[q], dst + (uint32_t)h * HALF_B + (uint32_t)q * 4096u);
-        }
+        gdma4<4096>(base, voff[0], voff[1], voff[2], voff[3], dst + (uint32_t)h * HALF_B);
       } else {
         const auto r = b_rsrc(p.n0, p.kt, h);
-        if constexpr (ND_DMA_BURST) {
-          dma4<4096>(r, voff[0], voff[1], voff[2], voff[3], dst + (uint32_t)h * HALF_B);
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) dma(r, voff[q], dst + (uint32_t)h * HALF_B + (uint32_t)q * 4096u);
-        }
+        dma4<4096>(r, voff[0], voff[1], voff[2], voff[3], dst + (uint32_t)h * HALF_B);
       }
     }
   };
@@ -602,20 +578,10 @@ __global__ void __launch_bounds__(512, 1) gemm_pp_kernel(const bf16_t* __restric
     const uint32_t dst = lds0 + (uint32_t)(s & 1) * BUF_B + (uint32_t)h * HALF_B + (uint32_t)wn * 1024u;
     if (!(ABL & 1024) && p.m0 + 128 * h + 128 <= M) {
       const char* base = A + ((int64_t)(p.m0 + 128 * h) * lda + (int64_t)p.kt * TKE) * ES;
-      if constexpr (ND_DMA_BURST) {
-        gdma4<4096>(base, voff[0], voff[1], voff[2], voff[3], dst);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gdma(base, voff[q], dst + (uint32_t)q * 4096u);
-      }
+      gdma4<4096>(base, voff[0], voff[1], voff[2], voff[3], dst);
     } else {
       const auto r = a_rsrc(p.m0, p.kt, h);
-      if constexpr (ND_DMA_BURST) {
-        dma4<4096>(r, voff[0], voff[1], voff[2], voff[3], dst);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dma(r, voff[q], dst + (uint32_t)q * 4096u);
-      }
+      dma4<4096>(r, voff[0], voff[1], voff[2], voff[3], dst);
     }
   };
 
@@ -904,7 +870,7 @@ ND_API int nd_gemm_pp_rope(const void* A, const void* B, void* C, int M, int N, 
 // nd_mlp_coef_set for A/B (set it only between steps: a forward saved in one form must be read back in it).
 int g_mlp_coef = [] {
   const char* e = getenv("ND_MLP_COEF");
-  return e ? (atoi(e) != 0) : ND_MLP_COEF_DEFAULT;
+  return e ? (atoi(e) != 0) : kMlpCoefDefault;
 }();
 template <int EPI, int F8 = 0, int Q = 0>
 int launch_mlp(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,

@@ -354,7 +354,7 @@ struct WppBf16 {
   static constexpr int KT = 64, EB = 2;
   static constexpr uint32_t HALF_B = 64 * 128 * 2;  // [64 k][128 cols] bf16
   static constexpr uint32_t BUF_B = 4 * HALF_B;     // A0 A1 B0 B1 = 64 KiB
-  static constexpr bool BURST = ND_DMA_BURST, SCALE = false;
+  static constexpr bool BURST = true, SCALE = false;
   struct Frags {
     bf16x8 a[8][2], b[4][2];
   };

@@ -47,9 +47,6 @@ __device__ __forceinline__ void gdma(const void* base, uint32_t voff, uint32_t l
 
 // Four pieces from per-lane byte offsets v0..v3 into LDS lds, lds + ST, lds + 2 ST, lds + 3 ST: m0 is saved /
 // restored once per burst and stepped with one s_add per piece (SCC is declared clobbered).
-#ifndef ND_DMA_BURST
-#define ND_DMA_BURST 1
-#endif
 template <uint32_t ST>
 __device__ __forceinline__ void gdma4(const void* base, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t lds) {
   uint32_t keep;

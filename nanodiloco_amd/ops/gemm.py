@@ -203,8 +203,14 @@ def set_w128(group_m: int = -1, nt: int = -1, ovl: int = -1) -> int:
 
 
 def set_pp_variant(v: int) -> int:
-    """Ablation builds of the ping-pong kernel (profiling only -- WRONG results): 1 no LDS-DMA in the
-    loop, 2 no fragment reads, 3 both, 4 no barriers, 8 no epilogue stores, 15 all; 0 = the kernel."""
+    """A/B variant of the ping-pong kernel (``pp_variant_ok`` in csrc/gemm_pp.hip); returns the previous
+    variant, or -1 when this build does not contain ``v`` (nothing changes then).
+    Correct results, every build: 0 the default; 32 plain-policy C stores (no nt); 256 direct stores (no LDS
+    staging of C); 288 both; 512 nt stores in the SwiGLU forward epilogue; 1024 buffer-form LDS-DMA pieces
+    for every tile; 2048 sc1 + nt C stores; 2080 sc1 C stores.
+    WRONG results, timing only, accepted only by the -DND_ABLATION build (``csrc/build.py --ablation``):
+    1 no LDS-DMA in the loop, 2 no fragment reads, 4 no barriers, 8 no epilogue, 16 no vmcnt waits,
+    64 fragment reads ahead of the DMA issue, 128 every tile stored over tile 0, and their sums."""
     return int(_ext.lib().nd_gemm_pp_set_variant(int(v)))
 
 

@@ -129,10 +129,10 @@ def wgrad_accumulate(gw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor):
 
 
 # ---- which GEMM runs the PLAIN projection products (forward / input gradient, lm head)
-#   "blas" hipBLASLt through torch.mm -- the default: over the ten plain Llama-150M products the own kernels
-#          reach 0.924x (pp) / 0.920x (w128) of it per shape, and the bf16 step is 1.9 % (pp) / 3.2 % (w128)
-#          slower with them (round 5, gpurun_out r5a / r5k; profiles/r5_gemm.md); the task brief allows a
-#          library for PLAIN GEMMs -- every fused product and every weight gradient is on the own kernels
+#   "blas" hipBLASLt through torch.mm -- the default: over the ten plain Llama-150M products the own
+#          ping-pong kernel reaches 0.942x of it (w128 0.918x), and the bf16 step with --proj-gemm pp is
+#          0.983x (round 6, profiles/r6_gemm_vb.md); every fused product and every weight gradient is on
+#          the own kernels
 #   "pp"   own ping-pong MFMA kernel (csrc/gemm_pp.hip; ops.gemm.gemm_pp) for every projection
 #   "short" own kernel for the short-K products (K <= 1024: o forward / dgrad, lm-head logits); hipBLASLt for
 #          the long-K dgrads (0.86-0.94x there)
