@@ -96,13 +96,20 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
 }
 
 // ---- OCP fp8 (gfx950 v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32: e4m3fn / e5m2, RNE), saturating
+// Non-finite inputs: +-inf saturates to +-FMAX, NaN gives a NaN byte (so an fp8 GEMM fed a NaN activation
+// produces NaN instead of a healthy-looking -FMAX).  The clamp is IEEE-754-2019 minimum / maximum
+// (v_maximum3_f32 / v_minimum3_f32, NaN-propagating), two VALU per value like the fminf(fmaxf()) pair it
+// replaces: that pair compiles to a canonicalising v_max_f32 + v_med3_f32, which returns -FMAX for a NaN.
+__device__ __forceinline__ float clamp_keep_nan(float a, float lim) {
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(a, -lim), lim);
+}
 template <int FMT>  // 0: e4m3 (max 448), 1: e5m2 (max 57344)
 __device__ __forceinline__ uint32_t cvt4(float a, float b, float c, float d) {
   constexpr float FMAX = FMT == 0 ? 448.f : 57344.f;
-  a = fminf(fmaxf(a, -FMAX), FMAX);
-  b = fminf(fmaxf(b, -FMAX), FMAX);
-  c = fminf(fmaxf(c, -FMAX), FMAX);
-  d = fminf(fmaxf(d, -FMAX), FMAX);
+  a = clamp_keep_nan(a, FMAX);
+  b = clamp_keep_nan(b, FMAX);
+  c = clamp_keep_nan(c, FMAX);
+  d = clamp_keep_nan(d, FMAX);
   int r;
   if (FMT == 0) {
     r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);

@@ -2,6 +2,10 @@
 // saturates and converts to OCP fp8 (gfx950 v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32: e4m3fn / e5m2,
 // round-to-nearest-even) AND records amax(|x|) for the delayed-scaling recipe.
 //   out[i] = fp8(clamp(x[i] * scale, -FMAX, FMAX)),   amax_out = max(amax_out, max |x|)
+// x[i] * scale is one fp32 multiply of the widened input (subnormal products are kept, not flushed); the
+// conversion rounds to the nearest code, ties to even, and keeps the sign of zero.  Non-finite inputs: a NaN
+// gives a NaN byte (cvt4, common.h), +-inf saturates to +-FMAX and makes amax inf; amax is the maximum over the
+// non-NaN elements (fmaxf drops a NaN operand).  n == 0 launches one block that writes nothing.
 // The scale is read from device memory (no host sync).  8 elements per thread: 16-B bf16 loads,
 // 8-B fp8 stores; amax reduced per block, then one atomicMax (float as ordered int bits) per block
 // into one of `amax_parts` partial slots (blockIdx % parts): a single hot address serialises the
@@ -50,8 +54,12 @@ __global__ void __launch_bounds__(256) fp8_cast_kernel(const void* __restrict__ 
   }
 }
 
+static bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// x: 16-byte aligned (16-B loads); out: 8-byte aligned (8-B stores); refused before any launch otherwise.
 ND_API int nd_fp8_cast(const void* x, int xdt, int64_t n, const float* scale, void* out, int fmt, float* amax_out,
                        int amax_parts, hipStream_t s) {
+  if (!aligned(x, 16) || !aligned(out, 8)) return (int)hipErrorInvalidValue;
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;  // 8 blocks/CU, grid-stride beyond
@@ -73,7 +81,8 @@ ND_API int nd_fp8_cast(const void* x, int xdt, int64_t n, const float* scale, vo
 // plus amax.  64 x 64 tile per 256-thread block: each thread loads 2 x 8 consecutive elements
 // (16-B bf16 loads), writes them straight to `out`, and parks the fp8 bytes in LDS; the transposed
 // tile is then written as 16-B rows of outT (16 consecutive source rows of one column per thread).
-// rows and cols must be multiples of 64 (checked by the caller).
+// rows and cols must be multiples of 64, ld a multiple of 8; x and outT 16-byte aligned, out 8-byte aligned
+// (all checked by the launcher, which refuses with hipErrorInvalidValue before any launch).
 template <int XDT, int FMT>
 __global__ void __launch_bounds__(256) fp8_cast_t_kernel(const void* __restrict__ x, int rows, int cols, int64_t ld,
                                                          const float* __restrict__ scale_p, uint8_t* __restrict__ out,
@@ -125,6 +134,7 @@ __global__ void __launch_bounds__(256) fp8_cast_t_kernel(const void* __restrict_
 ND_API int nd_fp8_cast_t(const void* x, int xdt, int rows, int cols, int64_t ld, const float* scale, void* out,
                          void* outT, int fmt, float* amax_out, int amax_parts, hipStream_t s) {
   if (rows % 64 || cols % 64 || ld % 8 || outT == nullptr) return (int)hipErrorInvalidValue;
+  if (!aligned(x, 16) || !aligned(out, 8) || !aligned(outT, 16)) return (int)hipErrorInvalidValue;
   if (amax_parts < 1) amax_parts = 1;
   const dim3 g(cols / 64, rows / 64), b(256);
   uint8_t *o = (uint8_t*)out, *oT = (uint8_t*)outT;

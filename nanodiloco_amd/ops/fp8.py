@@ -139,10 +139,16 @@ def set_fused_quant(enabled: bool) -> None:
     _FUSED["enabled"] = bool(enabled)
 
 
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    """The kernels load 16 bytes at a time: a view that starts off a 16-byte boundary is copied to fresh storage
+    (the launchers refuse a misaligned pointer)."""
+    return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
+
+
 def cast(x: torch.Tensor, scale: torch.Tensor, fmt: int, amax: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp8(x * scale) with saturation.  ``amax`` (fp32, zero-initialised; any length P) accumulates
+    """fp8(x * scale) with saturation (NaN stays NaN).  ``amax`` (fp32, zero-initialised; any length P) accumulates
     max|x| as P partial maxima (true amax = ``amax.max()``), which keeps the atomics uncontended."""
-    x = x.contiguous()
+    x = _aligned16(x.contiguous())
     out = torch.empty(x.shape, dtype=TORCH_DT[fmt], device=x.device)
     _ext.check(_ext.lib().nd_fp8_cast(_ext.ptr(x), _ext.dtcode(x), x.numel(), _ext.ptr(scale), _ext.ptr(out), fmt,
                                       _ext.ptr(amax), amax.numel() if amax is not None else 1,
@@ -152,7 +158,7 @@ def cast(x: torch.Tensor, scale: torch.Tensor, fmt: int, amax: Optional[torch.Te
 
 def absmax_into(x: torch.Tensor, amax: torch.Tensor) -> None:
     """amax (zeroed by the caller; P partial slots) <- max|x| in one read of x (no output written)."""
-    x = x.contiguous()
+    x = _aligned16(x.contiguous())
     _ext.check(_ext.lib().nd_fp8_cast(_ext.ptr(x), _ext.dtcode(x), x.numel(), 0, 0, E4M3, _ext.ptr(amax), amax.numel(),
                                       _ext.stream_ptr(x.device)), "nd_fp8_cast(amax)")
 
@@ -161,8 +167,8 @@ def cast_t(x: torch.Tensor, scale: torch.Tensor, fmt: int, amax: Optional[torch.
            want_plain: bool = True):
     """(fp8(x * scale) or None, its transpose) in one pass; x is [rows, cols] with rows, cols % 64 == 0."""
     rows, cols = x.shape
-    if x.stride(1) != 1:
-        x = x.contiguous()
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.contiguous_format)
     out = torch.empty(rows, cols, dtype=TORCH_DT[fmt], device=x.device) if want_plain else None
     outT = torch.empty(cols, rows, dtype=TORCH_DT[fmt], device=x.device)
     _ext.check(_ext.lib().nd_fp8_cast_t(_ext.ptr(x), _ext.dtcode(x), rows, cols, x.stride(0), _ext.ptr(scale),

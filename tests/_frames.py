@@ -6,10 +6,13 @@ DEV = "cuda"
 
 
 def _ints(t):
-    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
-_PATTERN = {2: 0x7FC1, 4: 0x7FC12345}  # NaN payloads: a stray read shows as well as a stray write
+# NaN payloads: a stray read shows as well as a stray write.  One-byte elements (fp8, uint8) have no spare NaN
+# payload -- e4m3fn has a single NaN per sign, which a quantiser writes for a NaN input -- so their sentinel is
+# 0xA5: a finite negative code in both fp8 formats (e4m3 -0.203125, e5m2 -0.01953125).
+_PATTERN = {1: 0xA5, 2: 0x7FC1, 4: 0x7FC12345}
 
 
 def framed(rows, cols, dtype, pad_r=1, pad_c=16):

@@ -12,6 +12,10 @@ The error rule (``check``), per element:
   output stored as fp32:  |out - ref64| <= slack
   slack = margin * max|twin32 - ref64| over the same tensor, twin32 = the fp32 PyTorch twin on the same
   inputs (measured against the oracle, never against the kernel); margin 8 unless docs/PARITY.md says why not.
+
+The fp8 quantisers (``csrc/fp8.hip``, ``cvt4`` in ``csrc/common.h``) have no error rule: ``fp8_quantise`` gives the
+bytes from the 256-entry code tables (``fp8_codes``), ``fp8_probes`` the inputs at which a conversion can go wrong;
+``tests/test_fp8_quant_edges_gpu.py`` compares bytes.
 """
 import math
 
@@ -325,3 +329,88 @@ def outer_nesterov(master, sync, delta_sum, mom, inv_world, lr, momentum, first,
 # ------------------------------------------------------------------------------------------ transpose
 def transpose(x):
     return x.double().t()
+
+
+# ------------------------------------------------------------------------------------------ fp8 quantisers
+FP8_FMAX = {0: 448.0, 1: 57344.0}  # fmt 0: e4m3fn, 1: e5m2 (ops/fp8.py E4M3 / E5M2)
+_FP8_LAYOUT = {0: (4, 3, 7), 1: (5, 2, 15)}  # exponent bits, mantissa bits, bias
+_FP8_NAN_BYTE = 0x7F  # a NaN code in both formats (e4m3fn: S.1111.111; e5m2: S.11111.11)
+
+
+def fp8_codes(fmt):
+    """The 256 decoded values of OCP e4m3fn (fmt 0) / e5m2 (fmt 1) as float64, indexed by the byte.
+    e4m3fn: no infinities, only S.1111.111 is NaN (largest finite 448); e5m2: IEEE-like, exponent 31 is inf / NaN."""
+    eb, mb, bias = _FP8_LAYOUT[fmt]
+    vals = []
+    for byte in range(256):
+        sign = -1.0 if byte & 0x80 else 1.0
+        e, m = (byte >> mb) & ((1 << eb) - 1), byte & ((1 << mb) - 1)
+        if fmt == 0 and e == 15 and m == 7:
+            v = float("nan")
+        elif fmt == 1 and e == 31:
+            v = float("inf") if m == 0 else float("nan")
+        elif e == 0:
+            v = m * 2.0 ** (1 - bias - mb)
+        else:
+            v = (1.0 + m * 2.0 ** -mb) * 2.0 ** (e - bias)
+        vals.append(sign * v)
+    return torch.tensor(vals, dtype=torch.float64)
+
+
+def _fp8_finite(fmt):
+    """The finite non-negative code values in byte order (byte b decodes to element b; strictly increasing)."""
+    c = fp8_codes(fmt)[:128]
+    return c[torch.isfinite(c)]
+
+
+def fp8_quantise(x, scale, fmt):
+    """The bytes (uint8) of ``fp8(clamp(x * scale, -FMAX, FMAX))`` as csrc/fp8.hip states it: the product is ONE
+    fp32 multiply of the widened input (bf16 widens exactly) by the fp32 scale -- taken here as the exact float64
+    product of the two rounded once to fp32, subnormal results kept; the clamped value goes to the nearest finite
+    code of its own sign, ties to the code with an even low bit, -0 to 0x80; NaN gives a NaN code (compare with
+    ``fp8_is_nan``, not by byte); +-inf saturates to +-FMAX.  No float8 dtype and no kernel is involved."""
+    s = float(torch.as_tensor(scale).float().reshape(-1)[0])  # the fp32 scale (a number or a one-element tensor)
+    p = (x.double() * s).float().double()  # 24 x 24 significant bits: exact in float64, then one rounding
+    finite = _fp8_finite(fmt).to(x.device)
+    mids = (finite[:-1] + finite[1:]) / 2  # exact: a code has at most 4 significant bits
+    a = p.abs().clamp(max=FP8_FMAX[fmt])  # NaN stays NaN
+    nan = torch.isnan(a)
+    a = torch.where(nan, torch.zeros_like(a), a)
+    lo = torch.searchsorted(mids, a.reshape(-1).contiguous()).reshape(a.shape)  # number of midpoints below a
+    tie = mids[lo.clamp(max=mids.numel() - 1)] == a
+    code = torch.where(tie & (lo % 2 == 1), lo + 1, lo)
+    code = code | (torch.signbit(p).long() << 7)
+    code = torch.where(nan, torch.full_like(code, _FP8_NAN_BYTE), code)
+    return code.to(torch.uint8)
+
+
+def fp8_is_nan(q, fmt):
+    """Which bytes of ``q`` (uint8 or a float8 tensor) decode to NaN."""
+    return torch.isnan(fp8_codes(fmt).to(q.device)[q.view(torch.uint8).long()])
+
+
+def fp8_same(q, ref, fmt):
+    """Byte equality, with every NaN code equal to every other NaN code."""
+    q, ref = q.view(torch.uint8), ref.view(torch.uint8)
+    return (q == ref) | (fp8_is_nan(q, fmt) & fp8_is_nan(ref, fmt))
+
+
+def _ulp_step(v, up):
+    """Positive finite ``v`` (fp32 or bf16) moved one ulp of its dtype up or down."""
+    it = torch.int32 if v.dtype == torch.float32 else torch.int16
+    return (v.view(it) + (1 if up else -1)).view(v.dtype)
+
+
+def fp8_probes(fmt, dtype):
+    """The inputs at which a quantiser can round wrongly, as a 1-D CPU tensor of ``dtype`` (fp32 or bf16): every
+    finite non-negative code value; every midpoint of adjacent codes (the first is half the smallest subnormal);
+    each midpoint moved one ulp of ``dtype`` either way; FMAX moved up one ulp, 1e30 and inf; all of these negated;
+    +-0.  Code values and midpoints have at most 5 significant bits and exponents bf16 holds: exact in both dtypes.
+    NaN is kept apart (``float('nan')`` is added by the tests that want it)."""
+    finite = _fp8_finite(fmt)
+    mids = ((finite[:-1] + finite[1:]) / 2).to(dtype)
+    assert bool((mids.double() * 2 == finite[:-1] + finite[1:]).all())
+    fmax = torch.tensor([FP8_FMAX[fmt]], dtype=dtype)
+    pos = torch.cat([finite.to(dtype), mids, _ulp_step(mids, False), _ulp_step(mids, True), _ulp_step(fmax, True),
+                     torch.tensor([1e30, float("inf")], dtype=dtype)])
+    return torch.cat([pos, -pos, torch.tensor([0.0, -0.0], dtype=dtype)])

@@ -52,6 +52,7 @@ def test_cast_t_matches_torch(fmt, dt):
     big = torch.randn(128, 256, device="cuda").to(dt)
     q2, qt2 = fp8.cast_t(big[:, 64:192], scale, fmt)
     ref2 = (big[:, 64:192].float() * 11.0).clamp(-fp8.FMAX[fmt], fp8.FMAX[fmt]).to(fp8.TORCH_DT[fmt])
+    assert torch.equal(q2.view(torch.uint8), ref2.view(torch.uint8))
     assert torch.equal(qt2.view(torch.uint8), ref2.t().contiguous().view(torch.uint8))
 
 

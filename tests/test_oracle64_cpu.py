@@ -385,3 +385,102 @@ def test_attention_twin_is_a_bf16_operand_model(mode):
         d = (a[fin] - b[fin]).abs().max().item()
         assert 0.0 < d < 2.0 ** -6 * b[fin].abs().max().item(), (k, d, b[fin].abs().max().item())
     assert tw["lse2"].dtype == torch.float32 and tw["delta"].dtype == torch.float32
+
+
+# ------------------------------------------------------------------------------------------ fp8 code tables
+FP8_DT = {0: torch.float8_e4m3fn, 1: torch.float8_e5m2}
+FP8_SCALES = [1.0, 2.0 ** -3, 2.0 ** 5, 37.5]
+
+
+@pytest.mark.parametrize("fmt", [0, 1])
+def test_fp8_code_table(fmt):
+    """The table from the format definition: 256 values, sign symmetry, FMAX, the smallest subnormal, the NaN /
+    inf codes, strictly increasing finite codes -- and the same values torch decodes (decoding is exact)."""
+    c = o64.fp8_codes(fmt)
+    assert c.shape == (256,) and c.dtype == torch.float64
+    fin = torch.isfinite(c)
+    assert c[fin].abs().max().item() == o64.FP8_FMAX[fmt]
+    assert c[1].item() == (2.0 ** -9 if fmt == 0 else 2.0 ** -16) and c[0].item() == 0.0
+    assert bool(torch.signbit(c[128])) and c[128].item() == 0.0
+    assert torch.equal(c[128:][fin[128:]], -c[:128][fin[:128]])
+    nan = [b for b in range(256) if c[b] != c[b]]
+    assert nan == ([0x7F, 0xFF] if fmt == 0 else [0x7D, 0x7E, 0x7F, 0xFD, 0xFE, 0xFF])
+    assert (fmt == 0 and not torch.isinf(c).any()) or (c[0x7C].item() == float("inf") and c[0xFC].item() == -float("inf"))
+    f = c[:128][fin[:128]]
+    assert f.numel() == (127 if fmt == 0 else 124) and bool((f[1:] > f[:-1]).all())
+    dec = torch.arange(256, dtype=torch.uint8).view(FP8_DT[fmt]).double()
+    assert torch.equal(dec.nan_to_num(nan=12345.0), c.nan_to_num(nan=12345.0))
+    assert torch.equal(torch.signbit(dec)[~torch.isnan(c)], torch.signbit(c)[~torch.isnan(c)])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("fmt", [0, 1])
+def test_fp8_probes_hold_what_they_claim(fmt, dtype):
+    p = o64.fp8_probes(fmt, dtype)
+    assert p.dtype == dtype and p.numel() == (1018 if fmt == 0 else 994) and not torch.isnan(p).any()
+    c = o64.fp8_codes(fmt)
+    f = c[:128][torch.isfinite(c[:128])]
+    have = set(p.double().tolist())
+    for v in f.tolist() + ((f[:-1] + f[1:]) / 2).tolist():
+        assert v in have and -v in have
+    half = f[1].item() / 2  # half the smallest subnormal and its two neighbours
+    nb = torch.tensor([half], dtype=dtype)
+    for v in (half, o64._ulp_step(nb, True).item(), o64._ulp_step(nb, False).item()):
+        assert v in have
+    assert o64._ulp_step(torch.tensor([o64.FP8_FMAX[fmt]], dtype=dtype), True).item() in have
+    assert float("inf") in have and -float("inf") in have
+    assert int((p == 0).sum()) == 4 and int(torch.signbit(p[p == 0]).sum()) == 2
+
+
+@pytest.mark.parametrize("scale", FP8_SCALES)
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("fmt", [0, 1])
+def test_fp8_quantise_matches_torch_on_the_probes(fmt, dtype, scale):
+    """The oracle (a search in the code table) == torch's multiply, clamp and float8 conversion, byte for byte, on
+    every probe; for the power-of-two scales ``probe / scale`` is passed so that the product is the probe."""
+    p = o64.fp8_probes(fmt, dtype)
+    x = (p.double() / scale).to(dtype) if scale != 37.5 else p
+    if scale != 37.5:
+        fin = torch.isfinite(p) & ((p.double() / scale).abs() < 3e38)
+        assert torch.equal((x.double() * scale)[fin], p.double()[fin])  # exact: lands on the probe
+    F = o64.FP8_FMAX[fmt]
+    ref = x.float().mul(scale).clamp(-F, F).to(FP8_DT[fmt]).view(torch.uint8)
+    got = o64.fp8_quantise(x, scale, fmt)
+    assert got.dtype == torch.uint8 and got.shape == x.shape
+    bad = (got != ref).nonzero().reshape(-1).tolist()
+    assert not bad, [(x[i].item(), hex(got[i]), hex(ref[i])) for i in bad[:8]]
+    assert not o64.fp8_is_nan(got, fmt).any()
+    # the rules, stated once without torch: ties to the even code, sign of zero, saturation
+    one = lambda v: int(o64.fp8_quantise(torch.tensor([v], dtype=torch.float32), 1.0, fmt)[0])  # noqa: E731
+    c = o64.fp8_codes(fmt)
+    assert one(-0.0) == 0x80 and one(0.0) == 0
+    assert one((c[1].item() + c[2].item()) / 2) == 2 and one((c[2].item() + c[3].item()) / 2) == 2
+    assert one(c[1].item() / 2) == 0 and one(-c[1].item() / 2) == 0x80
+    top = 0x7E if fmt == 0 else 0x7B
+    assert one(float("inf")) == top and one(-1e30) == top | 0x80 and one(F) == top
+
+
+@pytest.mark.parametrize("fmt", [0, 1])
+def test_fp8_quantise_nan(fmt):
+    """NaN in, a NaN code out -- in the oracle and in torch's conversion (clamp keeps NaN), whatever the byte."""
+    x = torch.tensor([1.0, float("nan"), -float("nan"), 3.0])
+    F = o64.FP8_FMAX[fmt]
+    for scale in FP8_SCALES:
+        got = o64.fp8_quantise(x, scale, fmt)
+        ref = x.mul(scale).clamp(-F, F).to(FP8_DT[fmt])
+        assert o64.fp8_is_nan(got, fmt).tolist() == [False, True, True, False]
+        assert o64.fp8_is_nan(ref, fmt).tolist() == [False, True, True, False]
+        assert torch.isnan(ref.float()).tolist() == [False, True, True, False]
+        assert bool(o64.fp8_same(got, ref, fmt).all())
+
+
+@pytest.mark.parametrize("fmt", [0, 1])
+def test_fp8_quantise_matches_torch_on_random_products(fmt):
+    """Off the probes: 200 000 random fp32 values over the whole range of the format at scale 37.5, where the product
+    is inexact and its one rounding to fp32 (not the float64 product) decides the side of a midpoint."""
+    g = torch.Generator().manual_seed(1)
+    F = o64.FP8_FMAX[fmt]
+    x = torch.randn(200000, generator=g) * torch.exp2(torch.randint(-20, 12, (200000,), generator=g).float())
+    ref = x.mul(37.5).clamp(-F, F).to(FP8_DT[fmt]).view(torch.uint8)
+    assert torch.equal(o64.fp8_quantise(x, 37.5, fmt), ref)
+    assert torch.equal(o64.fp8_quantise(x, torch.tensor([37.5]), fmt), ref)  # the scale as a one-element tensor
