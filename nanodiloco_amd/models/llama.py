@@ -98,6 +98,7 @@ class LlamaForCausalLM:
         self._wt_cache = {}
         self.training = True
         self.fp8 = None
+        self._fp8_off = False  # loss_stats: the evaluation forward of an fp8 model runs the bf16 projections
         if fp8:
             if compute_dtype != torch.bfloat16 or self.device.type != "cuda":
                 raise ValueError("fp8 needs bf16 compute on an MI355X")
@@ -186,7 +187,7 @@ class LlamaForCausalLM:
                 e[1] = self.store.version
 
     def _fp8_on(self, key: str) -> bool:
-        if self.fp8 is None:
+        if self.fp8 is None or self._fp8_off:
             return False
         from ..ops.fp8 import fp8_projection
         return fp8_projection(key.split(".")[1])
@@ -223,7 +224,7 @@ class LlamaForCausalLM:
                                 c.head_dim, rope_cols)
             rotated = True
         else:
-            if self.fp8 is not None and not fp8_qkv:
+            if self.fp8 is not None and not fp8_qkv and not self._fp8_off:
                 _warn_once("qkv", "--fp8-keep-fused rope: the fused bf16 q|k|v + RoPE GEMM cannot run on this "
                                   "shape; the projection runs as a plain bf16 GEMM + separate RoPE pass (slower "
                                   "than fp8)")
@@ -246,7 +247,7 @@ class LlamaForCausalLM:
                 m = ops.mlp_fused(y, w_gu, self._fused(gn, "grad"), wt_gu, w_dn,
                                   self._g(p + "mlp.down_proj.weight"), wt_dn)
                 return m, h
-            if self.fp8 is not None:
+            if self.fp8 is not None and not self._fp8_off:
                 _warn_once("mlp", "--fp8-keep-fused mlp: the fused bf16 SwiGLU GEMMs cannot run on this shape; "
                                   "the MLP runs as plain bf16 GEMMs + separate SwiGLU passes (slower than fp8)")
         elif self.fp8.mlp_ok(y, w_gu, w_dn):
@@ -334,3 +335,29 @@ class LlamaForCausalLM:
                 B, T = input_ids.shape
                 out.logits = ops.mm_nt(y.detach(), self._w(lm)).float().view(B, T, -1)
         return out
+
+    @torch.no_grad()
+    def loss_stats(self, input_ids: torch.Tensor, labels: torch.Tensor, attention_mask=None) -> torch.Tensor:
+        """Evaluation of one batch: float64 ``[sum of row losses, valid tokens, top-1 hits]`` on the device (no
+        host sync), so batches -- and ranks -- add up before anything is divided.  ``labels`` follow HF semantics
+        as in ``forward`` (shifted internally, -100 ignored); ``doc_mask`` / ``attention_mask`` and the residual
+        dtype act as they do there.
+
+        The call leaves no trace: it runs under ``no_grad`` with the gradient views off (nothing is written to the
+        flat grad buffer), takes the loss-only lm head (``ops.lm_head_loss``: one GEMM per chunk, the logits are
+        only read) and restores ``training``.  With fp8 the evaluation forward runs the bf16 projections on the
+        bf16 shadow weights: no activation is quantised, so neither the delayed-scaling state of ``Fp8Recipe``
+        (amax partials, history, scales, first-use flags) nor the ``Fp8Weight`` caches are read or written, the
+        next training step is bitwise what it would have been without the evaluation, and the number does not
+        depend on the scaling history."""
+        was_training, was_off, lm_y8 = self.training, self._fp8_off, getattr(self, "_lm_y8", None)
+        self.training, self._fp8_off = False, True
+        try:
+            y = self.hidden_states(input_ids, attention_mask)
+            lm = "lm_head.weight" if not self.config.tie_word_embeddings else "model.embed_tokens.weight"
+            targets = ops.reference.shift_labels(labels, ops.IGNORE_INDEX).reshape(-1)
+            row_loss, row_hit = ops.lm_head_loss(y, self._w(lm), targets)
+        finally:
+            self.training, self._fp8_off, self._lm_y8 = was_training, was_off, lm_y8
+        return torch.stack([row_loss.sum(dtype=torch.float64), (targets != ops.IGNORE_INDEX).sum().double(),
+                            row_hit.sum().double()])

@@ -161,6 +161,8 @@ def _declare(L: ctypes.CDLL):
         # loss
         "nd_ce_fwd_bwd": [P, I, P, P, P, L64, I, I, P, P, F, P],
         "nd_ce_fwd_bwd_q8": [P, I, P, P, P, L64, I, I, P, P, P, P, P, I, I, P],
+        # loss only (evaluation, csrc/ce_loss.hip): const logits, per-row loss / lse / top-1 hit
+        "nd_ce_loss": [P, I, P, L64, I, I, P, P, P, P],
         # embedding
         "nd_embedding_fwd": [P, P, P, I, L64, I, I, P],
         "nd_embedding_bwd": [P, P, I, P, L64, I, I, P],

@@ -49,6 +49,15 @@ def _chunk_rows(V: int, elem: int, budget_bytes: int = 0) -> int:
     return max(256, ((budget_bytes or _CHUNK_BYTES) // (V * elem)) // 256 * 256)
 
 
+def _chunks(n: int, V: int, elem: int, chunk_rows: int):
+    """The [start, end) row chunks of the lm head: ``chunk_rows`` as given, else the logits budget."""
+    chunk = chunk_rows or _chunk_rows(V, elem)
+    if not chunk_rows and n > chunk:  # equal-sized chunks: one GEMM shape, one tuned kernel
+        nch = -(-n // chunk)
+        chunk = (-(-n // nch) + 255) // 256 * 256
+    return [(s, min(n, s + chunk)) for s in range(0, n, chunk)]
+
+
 class LMHeadCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None):
@@ -74,12 +83,7 @@ class LMHeadCEFn(torch.autograd.Function):
             wq = lin.weights[LM_KEY].get(w, version)
             if pp_f8_supported(y8, wq.w8) and V % 128 == 0:
                 q = (r, kx, kdy, y8, wq)
-        chunk = chunk_rows or _chunk_rows(V, y.element_size() if hip else 4)
-        if not chunk_rows and n > chunk:  # equal-sized chunks: one GEMM shape, one tuned kernel
-            nch = -(-n // chunk)
-            chunk = (-(-n // nch) + 255) // 256 * 256
-        for s in range(0, n, chunk):
-            e = min(n, s + chunk)
+        for s, e in _chunks(n, V, y.element_size() if hip else 4, chunk_rows):
             yc, tc = y[s:e], targets[s:e]
             if hip:
                 if q is not None:  # fp8: e4m3 x e4m3 on the own fp8 ping-pong kernel
@@ -160,3 +164,36 @@ def lm_head_ce(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torc
     """``wt``: optional W^T copy [d, V] for the input-gradient GEMM (see ops/linear.py).  ``f8``:
     (Fp8Linears, weight version, fused e4m3 copy of y or None) for the fp8 lm head."""
     return LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8)
+
+
+@torch.no_grad()
+def lm_head_loss(y: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, chunk_rows: int = 0):
+    """Loss-only lm head for evaluation: ``(row_loss [n] fp32, row_hit [n] bool)``.
+
+    Per chunk ``logits = y_c @ W^T`` (the plain projection GEMM) and ``nd_ce_loss``: one of ``lm_head_ce``'s three
+    GEMMs, no gradient written over the logits, no ``dy``.  ``row_loss`` = logsumexp - logit[target] (0 where the
+    target is ``IGNORE_INDEX``); ``row_hit`` = the target's logit equals the row maximum (top-1, ties count, exact on
+    the stored logits; False on ignored rows and on rows that hold a NaN).  Per-row stores only -- no atomics -- so
+    the result is bitwise repeatable with or without the deterministic mode.  Always bf16 / fp32, never the fp8
+    lm head.  CPU / ``--ops torch``: fp32 logits, as ``lm_head_ce``."""
+    n, V = y.shape[0], w.shape[0]
+    targets = targets.reshape(-1)
+    row_loss = torch.empty(n, dtype=torch.float32, device=y.device)
+    row_hit = torch.empty(n, dtype=torch.bool, device=y.device)
+    hip = _ext.use_hip(y)
+    for s, e in _chunks(n, V, y.element_size() if hip else 4, int(chunk_rows)):
+        yc, tc = y[s:e], targets[s:e]
+        if hip:
+            logits = mm_nt(yc, w)
+            _ext.check(_ext.lib().nd_ce_loss(_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc), e - s, V,
+                                             IGNORE_INDEX, _ext.ptr(row_loss[s:e]), 0, _ext.ptr(row_hit[s:e]),
+                                             _ext.stream_ptr(y.device)), "nd_ce_loss")
+        else:
+            logits = torch.mm(yc.float(), w.float().t())
+            lse = torch.logsumexp(logits, dim=-1)
+            ok = tc != IGNORE_INDEX
+            tgt = torch.where(ok, tc, torch.zeros_like(tc))
+            picked = logits.gather(1, tgt[:, None])[:, 0]
+            row_loss[s:e] = torch.where(ok, lse - picked, torch.zeros_like(lse))
+            row_hit[s:e] = ok & (picked == logits.max(dim=-1).values) & ~torch.isnan(lse)
+    return row_loss, row_hit

@@ -20,7 +20,8 @@ import torch
 
 from . import ops
 from .config import LlamaConfig, default_run_config, load_config_from_file, resolve_llama_config
-from .data import build_data
+from .data import build_data, build_eval_data
+from .evaluate import evaluate_model
 from .models import LlamaForCausalLM
 from .optim import FlatAdamW, FlatOuterNesterov
 from .parallel.diloco import Diloco
@@ -103,6 +104,10 @@ class TrainArgs:
     mask_pad_labels: bool = True
     doc_mask: bool = False         # packed data (memmap / synthetic): attention stays inside each EOS-separated
                                    # document of a window (block-diagonal causal; ops.doc_bounds, docs/DESIGN.md)
+    eval_every: int = 0            # held-out evaluation every N inner steps and once after the last (0 = off);
+                                   # Trainer.evaluate, docs/DESIGN.md "Held-out evaluation"
+    eval_batches: int = 8          # micro-batches of --per-device-batch-size per rank and evaluation
+    eval_dataset_path: Optional[str] = None  # --data memmap: held-out shards (a directory of *.bin, or a glob)
     deterministic: bool = False    # bitwise-reproducible step: no float atomics (ops/determinism.py)
     skip_nonfinite: bool = False   # device-side skip of inner steps whose grad norm is NaN/Inf (no host sync)
     collective_timeout_s: float = 1800.0
@@ -247,6 +252,16 @@ class Trainer:
                                batch_size=a.per_device_batch_size, seed=a.seed, rank=e.rank, world_size=e.world_size,
                                device=e.device, dataset_path=a.dataset_path, tokenizer=a.tokenizer,
                                mask_pad_labels=a.mask_pad_labels)
+        # held-out stream (--eval-every): its own generator / shards and cursor, never the training stream's
+        self.eval_data = None
+        if a.eval_every > 0:
+            if a.eval_batches < 1:
+                raise ValueError("--eval-batches must be at least 1")
+            self.eval_data = build_eval_data(self.data_kind, vocab_size=self.llama_config.vocab_size,
+                                             seq_len=a.seq_length, batch_size=a.per_device_batch_size, seed=a.seed,
+                                             rank=e.rank, world_size=e.world_size, device=e.device,
+                                             eval_dataset_path=a.eval_dataset_path)
+        self._eval_wall = 0.0  # seconds of evaluation since the last training log record
         self.start_step = 0
         resume = a.resume
         if resume == "auto":  # restart form: the newest complete checkpoint of --checkpoint-dir, else fresh
@@ -322,6 +337,22 @@ class Trainer:
             self.diloco.inner_step()
         return loss_sum / self.grad_accum
 
+    def evaluate(self, step: Optional[int] = None) -> Dict[str, Any]:
+        """Held-out evaluation of the weights this rank holds now: ``eval_batches`` batches of the (rewound) eval
+        stream through ``model.loss_stats``, summed on the device, all-reduced (SUM) over the whole world -- with
+        ``--inner-dp`` every rank holds different eval data -- and divided once: the loss is token-weighted, not a
+        mean of batch means (evaluate.evaluate_model).  One host sync.  A collective: every rank calls it at the same
+        steps.  Logs its own record and returns it."""
+        if self.eval_data is None:
+            raise RuntimeError("evaluation is off: the run has no held-out stream (--eval-every 0)")
+        with self.timer.phase("eval"):
+            rec = evaluate_model(self.model, self.eval_data, self.args.eval_batches, self.env.device)
+        self._eval_wall += rec["eval_s"]
+        if step is not None:
+            rec = {"step": int(step), **rec}
+        self.sink.log(rec)
+        return rec
+
     def train(self) -> Dict[str, Any]:
         a, e = self.args, self.env
         self.model.train()
@@ -350,7 +381,8 @@ class Trainer:
             if (a.log_every and real_step % a.log_every == 0) or real_step == a.total_steps:
                 lv = float(loss.item())
                 now = time.perf_counter()
-                dt = now - last_t
+                dt = now - last_t - self._eval_wall  # evaluation is not training time
+                self._eval_wall = 0.0
                 tps = tokens_per_step * (real_step - last_step) * e.world_size / max(dt, 1e-9)
                 last_t, last_step, last_loss = now, real_step, lv
                 metrics = {
@@ -374,6 +406,10 @@ class Trainer:
                     metrics["comm_ms"] = self.diloco.comm_ms()
                 metrics.update(self.timer.report())
                 self.sink.log(metrics)
+            # held-out evaluation; the one at the last step is left to the evaluation after finalize() below
+            if a.eval_every > 0 and real_step % a.eval_every == 0 and \
+                    (real_step < a.total_steps or a.stop_at_step):
+                self.evaluate(real_step)
             if did_outer and a.checkpoint_dir and a.checkpoint_every and \
                     (real_step // a.inner_steps) % a.checkpoint_every == 0:
                 self.save(real_step)
@@ -384,12 +420,18 @@ class Trainer:
             self.diloco.flush_fragments()  # every fragment once more: master == theta_sync on every worker
         else:
             self.diloco.finalize()
+        final_eval = None
+        if a.eval_every > 0 and not a.stop_at_step:
+            final_eval = self.evaluate(a.total_steps)  # the finished model (master == theta_sync on every worker)
         if a.checkpoint_dir and not a.stop_at_step:
             self.save(a.total_steps)
         if e.rank == 0:
             print("Training completed!", flush=True)
         self.sink.finish()
-        return {"final_loss": last_loss, "steps": a.total_steps, "outer_steps": self.diloco.outer_step_count}
+        out = {"final_loss": last_loss, "steps": a.total_steps, "outer_steps": self.diloco.outer_step_count}
+        if final_eval is not None:
+            out["final_eval_loss"] = final_eval["eval_loss"]
+        return out
 
     def save(self, step: int):
         from .utils.checkpoint import save_checkpoint
