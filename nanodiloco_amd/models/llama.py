@@ -21,7 +21,9 @@ backward; see ``_GradHook`` for why the hook sits on the next norm's input).
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
+import functools
 from typing import Callable, List, Optional
 
 import torch
@@ -32,6 +34,7 @@ from ..ops.cross_entropy import LM_KEY
 from .param_store import ParamStore
 
 _WARNED = set()
+_CONFIG = object()  # generate(): "take it from the model config"
 
 
 def _warn_once(key: str, msg: str) -> None:
@@ -204,7 +207,7 @@ class LlamaForCausalLM:
             return None
         return self.fp8.dy_target(key) if grad else self.fp8.x_target(key)
 
-    def _layer(self, i, h, y, cos, sin, B, T, next_norm, y8=None, kstart=None, doc=None):
+    def _layer(self, i, h, y, cos, sin, B, T, next_norm, y8=None, kstart=None, doc=None, cache=None):
         c = self.config
         p = f"model.layers.{i}."
         cdt = self.compute_dtype
@@ -232,6 +235,10 @@ class LlamaForCausalLM:
             rotated = False
         o = ops.attention(qkv, cos, sin, B, T, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
                           inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc)
+        if cache is not None:
+            # prefill: the HIP path has rotated q|k inside qkv by now (in place, or in the GEMM epilogue); the
+            # PyTorch path leaves its input alone and cache_fill rotates k itself
+            ops.cache_fill(cache, i, qkv, B, T, cos, sin, rotated=rotated or ops._ext.use_hip(qkv))
         a = self._linear(f"{i}.o", o, self._w(p + "self_attn.o_proj.weight"), self._g(p + "self_attn.o_proj.weight"))
         q_gu = self._q8(f"{i}.gu")
         y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"),
@@ -263,10 +270,12 @@ class LlamaForCausalLM:
                          q_down.out if q_down is not None else None)
         return m, h
 
-    def hidden_states(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def hidden_states(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                      cache=None) -> torch.Tensor:
         """Final-normed hidden states [B*T, d] in the compute dtype.  ``attention_mask`` (HF [B, T],
         left or right padded) becomes a per-sequence key start for the attention kernels.  With ``doc_mask`` the
-        document bounds of the packed window are derived from ``input_ids`` once and shared by every layer."""
+        document bounds of the packed window are derived from ``input_ids`` once and shared by every layer.
+        ``cache`` (an ``ops.KVCache``, prefill only): every layer's rotated k and v go into slots 0 .. T-1."""
         c = self.config
         if self.doc_mask and attention_mask is not None:
             raise ValueError("doc_mask (packed documents) and attention_mask (padded batches) cannot be combined")
@@ -298,7 +307,7 @@ class LlamaForCausalLM:
                 from torch.utils.checkpoint import checkpoint
                 m, h = checkpoint(self._layer, i, h, y, cos, sin, B, T, nxt, None, kstart, doc, use_reentrant=False)
             else:
-                m, h = self._layer(i, h, y, cos, sin, B, T, nxt, y8, kstart, doc)
+                m, h = self._layer(i, h, y, cos, sin, B, T, nxt, y8, kstart, doc, cache)
             if hook is not None and i + 1 < L:
                 # layer i+1's gradients are final once the backward of the add+norm that produces its
                 # input (and owns its input_layernorm weight) has run: hook that norm's input
@@ -361,3 +370,186 @@ class LlamaForCausalLM:
             self.training, self._fp8_off, self._lm_y8 = was_training, was_off, lm_y8
         return torch.stack([row_loss.sum(dtype=torch.float64), (targets != ops.IGNORE_INDEX).sum().double(),
                             row_hit.sum().double()])
+
+    # ------------------------------------------------------------------ generation
+    def _lm_name(self) -> str:
+        return "lm_head.weight" if not self.config.tie_word_embeddings else "model.embed_tokens.weight"
+
+    @contextlib.contextmanager
+    def _inference(self):
+        """What ``loss_stats`` does: gradient views off, and for an fp8 model the bf16 projections on the bf16 shadow
+        weights, so that nothing of the delayed-scaling state is read or written; everything restored on exit."""
+        saved = (self.training, self._fp8_off, getattr(self, "_lm_y8", None))
+        self.training, self._fp8_off = False, True
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            self.training, self._fp8_off, self._lm_y8 = saved
+
+    def new_cache(self, batch: int, s_max: int):
+        return ops.KVCache(self.config, batch, s_max, self.device, self.compute_dtype)
+
+    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], cache) -> torch.Tensor:
+        """The existing forward on a (left-padded) prompt batch [B, T], every layer's k|v into ``cache`` slots
+        0 .. T-1, ``pos = T``, ``kstart = ops.key_start(attention_mask)``.  Returns the last position's logits [B, V]
+        (fp32).  Positions are slot indices, the training path's convention under left padding (scores depend on
+        q - k only)."""
+        B, T = input_ids.shape
+        if self.doc_mask:
+            raise ValueError("generation runs on single documents: build the model without doc_mask")
+        if B != cache.batch or T > cache.s_max:
+            raise ValueError(f"a [{B}, {T}] prompt does not fit a KV cache of batch {cache.batch}, "
+                             f"s_max {cache.s_max}")
+        with self._inference():
+            y = self.hidden_states(input_ids, attention_mask, cache=cache)
+            cache.pos.fill_(T)
+            cache.max_pos = T
+            if attention_mask is not None:
+                cache.kstart.copy_(ops.key_start(attention_mask))
+            else:
+                cache.kstart.zero_()
+            last = y.view(B, T, -1)[:, -1].contiguous()
+            return ops.mm_nt(last, self._w(self._lm_name())).float()
+
+    def _decode_device(self, tokens: torch.Tensor, cache) -> torch.Tensor:
+        """The device work of one decode step (static shapes, no host sync: HIP-graph capturable), ``pos += 1``
+        included; the host-side bound of the cache is the caller's."""
+        c = self.config
+        cdt, eps = self.compute_dtype, c.rms_norm_eps
+        B = tokens.shape[0]
+        cos, sin = ops.rope_cache(cache.s_max, c.head_dim, c.rope_theta, c.rope_scaling, self.device)
+        h = ops.embedding(tokens.view(B, 1), self._m("model.embed_tokens.weight"), None, out_dtype=self.residual_dtype)
+        y, h = ops.rmsnorm_res(h, self._m("model.layers.0.input_layernorm.weight"), None, eps, cdt)
+        L = c.num_hidden_layers
+        for i in range(L):
+            p = f"model.layers.{i}."
+            qkv = ops.mm_nt(y, self._fused(self._qkv_names[i], "shadow"))
+            o = ops.attention_decode(qkv, cache, i, cos, sin)
+            a = ops.mm_nt(o, self._w(p + "self_attn.o_proj.weight"))
+            y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"), None, eps, cdt)
+            gu = ops.mm_nt(y, self._fused(self._gu_names[i], "shadow"))
+            m = ops.mm_nt(ops.swiglu(gu), self._w(p + "mlp.down_proj.weight"))
+            nxt = f"model.layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "model.norm.weight"
+            y, h = ops.add_rmsnorm(h, m, self._m(nxt), None, eps, cdt)
+        logits = ops.mm_nt(y, self._w(self._lm_name())).float()
+        cache.pos += 1
+        return logits
+
+    def decode_step(self, tokens: torch.Tensor, cache) -> torch.Tensor:
+        """One token per sequence (``tokens`` [B], at slot ``cache.pos``) -> next-token logits [B, V] (fp32)."""
+        cache.check_room()
+        with self._inference():
+            logits = self._decode_device(tokens, cache)
+        cache.advance(device_side=False)
+        return logits
+
+    def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                 max_new_tokens: int = 32, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                 eos_token_id=_CONFIG, pad_token_id=_CONFIG, seed: int = 0, use_cache: bool = True,
+                 hip_graph="auto", return_logits: bool = False):
+        """Continue a (left-padded) prompt batch ``input_ids`` [B, T]; returns the token ids [B, T + n], n <=
+        ``max_new_tokens`` (generation ends early once every row has produced ``eos_token_id``; a finished row is
+        filled with ``pad_token_id``).  ``temperature`` 0 is greedy; otherwise ``filter_logits`` (top-k, top-p) and
+        ``torch.multinomial`` with a generator seeded by ``seed``.  ``use_cache=False`` recomputes the whole prefix
+        per token (the check and the timing baseline).  ``hip_graph``: True / False / "auto" (on for a GPU, non-fp8
+        model on the HIP path): the decode step is captured once after two eager steps and replayed.
+        ``return_logits``: also the fp32 logits [B, n, V] every token was drawn from."""
+        c = self.config
+        eos = c.eos_token_id if eos_token_id is _CONFIG else eos_token_id
+        pad = pad_token_id
+        if pad is _CONFIG or pad is None:
+            pad = c.pad_token_id if c.pad_token_id is not None else (eos if eos is not None else 0)
+        B, T = input_ids.shape
+        n = int(max_new_tokens)
+        if n < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+            raise ValueError("need temperature >= 0, 0 < top_p <= 1, top_k >= 0")
+        if attention_mask is not None:
+            ops.check_padding(attention_mask)
+            if not bool(attention_mask[:, -1].all()):
+                raise ValueError("generation needs left-padded prompts (every row's last token real)")
+        dev = input_ids.device
+        gen = None
+        if temperature > 0:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+        if hip_graph == "auto":
+            hip_graph = use_cache and self.fp8 is None and ops._ext.get_backend() != "torch" and dev.type == "cuda"
+        if hip_graph and (not use_cache or dev.type != "cuda"):
+            raise ValueError("hip_graph needs use_cache=True on a GPU")
+        if use_cache:
+            cache = self.new_cache(B, T + n - 1)  # the last token drawn is never fed back
+            logits = self.prefill(input_ids, attention_mask, cache)
+            step = functools.partial(self.decode_step, cache=cache)
+            if hip_graph:
+                from ..utils.graphs import GraphedDecodeStep
+                step = GraphedDecodeStep(self, cache)
+        else:
+            if T + n - 1 > c.max_position_embeddings:
+                raise ValueError(f"{T} + {n} tokens exceed max_position_embeddings = {c.max_position_embeddings}")
+            ids = input_ids
+            mask = attention_mask
+            with self._inference():
+                logits = self.forward(ids, attention_mask=mask).logits[:, -1]
+        out = torch.full((B, n), pad, dtype=input_ids.dtype, device=dev)
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        kept = [] if return_logits else None
+        done = 0
+        for i in range(n):
+            if kept is not None:
+                kept.append(logits.clone())  # a graphed step returns its static buffer
+            tok = sample_logits(logits, temperature, top_k, top_p, gen).to(input_ids.dtype)
+            if eos is not None:
+                tok = torch.where(finished, torch.full_like(tok, pad), tok)
+                finished = finished | (tok == eos)
+            out[:, i] = tok
+            done = i + 1
+            if done == n or (eos is not None and done % 16 == 0 and bool(finished.all())):
+                break
+            if use_cache:
+                logits = step(tok)
+            else:
+                ids = torch.cat([ids, tok[:, None]], dim=1)
+                if mask is not None:
+                    mask = torch.cat([mask, torch.ones_like(mask[:, :1])], dim=1)
+                with self._inference():
+                    logits = self.forward(ids, attention_mask=mask).logits[:, -1]
+        if eos is not None:
+            # as HF: the result ends with the step at which the last row finished
+            hit = out[:, :done] == eos
+            first = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full_like(hit[:, 0].int(), done))
+            done = int(first.max())
+        res = torch.cat([input_ids, out[:, :done]], dim=1)
+        if return_logits:
+            return res, torch.stack(kept[:done], dim=1)
+        return res
+
+
+def filter_logits(logits: torch.Tensor, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+    """fp32 logits [B, V] with everything outside the top-k / nucleus set at -inf.  top-k keeps every logit >= the
+    k-th largest; top-p (applied to what top-k left) keeps, in descending order, every token whose preceding
+    probability mass is < ``top_p``.  Ties at either threshold are kept, so the result does not depend on the order
+    a sort gives equal logits."""
+    x = logits.float()
+    V = x.shape[-1]
+    if 0 < top_k < V:
+        kth = x.topk(top_k, dim=-1).values[..., -1:]
+        x = x.masked_fill(x < kth, float("-inf"))
+    if top_p < 1.0:
+        sl = x.sort(dim=-1, descending=True).values
+        pr = torch.softmax(sl, dim=-1)
+        before = pr.cumsum(-1) - pr
+        thr = sl.masked_fill(before >= top_p, float("inf")).amin(-1, keepdim=True)
+        x = x.masked_fill(x < thr, float("-inf"))
+    return x
+
+
+def sample_logits(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                  generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """One token id per row of fp32 ``logits`` [B, V]: argmax at temperature 0, else a seeded multinomial draw."""
+    if temperature == 0:
+        return logits.argmax(-1)
+    x = filter_logits(logits.float() / temperature, top_k, top_p)
+    return torch.multinomial(torch.softmax(x, dim=-1), 1, generator=generator)[:, 0]

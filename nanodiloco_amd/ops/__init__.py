@@ -10,6 +10,7 @@ from .embedding import embedding
 from .swiglu import swiglu
 from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding, doc_bounds, \
     check_doc_bounds
+from .decode import KVCache, attention_decode, cache_fill, decode_split
 from .cross_entropy import lm_head_ce, lm_head_loss, IGNORE_INDEX
 from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov, frag_pseudograd, frag_outer_mix, \
     SpanTable
@@ -21,6 +22,7 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "set_wgrad_overlap", "wgrad_overlap_enabled", "join_wgrad", "set_wgrad_group", "wgrad_group_enabled",
            "set_dgrad_transposed", "dgrad_transposed_enabled", "transpose_into",
            "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
+           "KVCache", "attention_decode", "cache_fill", "decode_split",
            "lm_head_ce", "lm_head_loss",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
            "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "frag_pseudograd", "frag_outer_mix", "SpanTable", "reference"]

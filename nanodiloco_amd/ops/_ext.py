@@ -153,6 +153,9 @@ def _declare(L: ctypes.CDLL):
         "nd_attn_bwd_pre": [P, P, P, I, I, I, L64, L64, P],
         "nd_attn_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
         "nd_attn_bwd_fused": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
+        # single-query attention against a KV cache, RoPE + append fused, split-KV + combine (csrc/attn_decode.hip)
+        "nd_attn_decode": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, P],
+        "nd_attn_decode_split": [],
         # mlp
         "nd_swiglu_fwd": [P, P, I, L64, I, P],
         "nd_swiglu_bwd": [P, P, P, I, L64, I, P],

@@ -63,3 +63,38 @@ class GraphedMicroStep:
         self.labels.copy_(labels, non_blocking=True)
         self.graph.replay()
         return self.loss
+
+
+class GraphedDecodeStep:
+    """One cached decode step of ``model.generate`` as a HIP graph: two eager warm-up steps on a side stream, then
+    ``model._decode_device`` (embedding .. logits, the cache append and ``pos += 1``) is captured once on static
+    token / logits buffers and every later step is a token copy plus ``replay()``.  Sampling stays outside.  The
+    capture is a single stream with no parallel branches; the decode kernels read the positions on the device, so
+    the same graph serves every step.  The returned logits are the graph's static buffer: valid until the next call."""
+
+    def __init__(self, model, cache, warmup: int = 2):
+        self.model, self.cache, self.warmup = model, cache, warmup
+        self.calls = 0
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.tokens = self.logits = None
+
+    def __call__(self, tokens: torch.Tensor) -> torch.Tensor:
+        self.cache.check_room()
+        if self.graph is None and self.calls < self.warmup:
+            self.calls += 1
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), self.model._inference():
+                logits = self.model._decode_device(tokens, self.cache)
+            torch.cuda.current_stream().wait_stream(side)
+            self.cache.advance(device_side=False)
+            return logits
+        if self.graph is None:
+            self.tokens = tokens.clone()
+            self.graph = torch.cuda.CUDAGraph()
+            with self.model._inference(), torch.cuda.graph(self.graph):  # records only; the replay below runs it
+                self.logits = self.model._decode_device(self.tokens, self.cache)
+        self.tokens.copy_(tokens, non_blocking=True)
+        self.graph.replay()
+        self.cache.advance(device_side=False)
+        return self.logits
