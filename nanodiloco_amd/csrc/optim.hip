@@ -5,6 +5,7 @@
 // Guideline 11).  The clip coefficient never touches the host: nd_adamw_step re-reduces the
 // <=1024 per-block sum-of-squares partials in every block (4 KB, L2-resident) before its stream.
 #include "common.h"
+#include "adamw_update.h"
 #include "outer_update.h"
 
 using namespace nd;
@@ -42,32 +43,10 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
                                                     float bc2, float max_norm, float* __restrict__ norm_out,
                                                     int skip_nonfinite, int* __restrict__ skipped) {
   __shared__ float red[4];
-  float coef = 1.f;
-  if (part) {
-    float t = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) t += part[i];
-    t = block_sum<256>(t, red);
-    const float norm = sqrtf(t);
-    if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));
-    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
-    // device-side guard: every block sees the same norm, so a NaN/Inf step is skipped everywhere
-    // (no host sync); the step counter on the host still advances, like torch's GradScaler skip.
-    if (skip_nonfinite && !isfinite(norm)) {
-      if (skipped && blockIdx.x == 0 && threadIdx.x == 0) skipped[0] += 1;
-      return;
-    }
-  }
-  const float decay = 1.f - lr * wd;
-  const float step = lr / bc1;
-  const float rbc2 = 1.f / sqrtf(bc2);
-  auto upd = [&](float& pp, float gg, float& mm, float& vv) {
-    gg *= coef;
-    pp *= decay;
-    mm = mm + omb1 * (gg - mm);
-    vv = vv * b2 + omb2 * gg * gg;
-    const float den = sqrtf(vv) * rbc2 + eps;
-    pp = pp - step * (mm / den);
-  };
+  const ClipState clip = clip_from_partials(part, nparts, max_norm, skip_nonfinite, norm_out, skipped, red);
+  if (clip.skip) return;
+  const AdamWCoef c(clip.coef, lr, wd, bc1, bc2, omb1, b2, omb2, eps);
+  auto upd = [&](float& pp, float gg, float& mm, float& vv) { adamw_update(c, pp, gg, mm, vv); };
   const int64_t n4 = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     float4 P = reinterpret_cast<float4*>(p)[i];

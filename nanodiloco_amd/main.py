@@ -19,6 +19,7 @@ from .trainer import TrainArgs, Trainer
 
 TRISTATE = {"hip_graph"}  # on | off | auto; the bare flag means "on"
 AUTO_INT = {"per_device_batch_size"}  # an int or "auto"
+CHOICES = {"inner_optimizer": ("adamw", "muon")}  # string flags with a closed set of values
 
 
 def _int_or_auto(s: str):
@@ -45,7 +46,7 @@ def build_parser() -> argparse.ArgumentParser:
         elif f.name in TRISTATE:
             p.add_argument(flag, type=str, nargs="?", const="on", default=default)  # bare flag = on
         else:
-            p.add_argument(flag, type=str, default=default)
+            p.add_argument(flag, type=str, default=default, choices=CHOICES.get(f.name))
     return p
 
 

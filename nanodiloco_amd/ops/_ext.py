@@ -179,6 +179,8 @@ def _declare(L: ctypes.CDLL):
         # streaming DiLoCo: fragment outer step through a span table (csrc/stream_outer.hip)
         "nd_frag_pseudograd": [P, P, P, I, L64, P, I, P],
         "nd_frag_outer_mix": [P, P, P, I, P, P, I, P, I, L64, F, F, F, I, F, P],
+        # Muon inner optimizer (csrc/muon.hip): AdamW over a span table
+        "nd_adamw_step_spans": [P, P, P, P, P, I, P, I, L64, P, I, F, D, D, F, F, F, F, F, P, I, P, P],
         # block-quantised outer transport (csrc/qcomm.hip)
         "nd_pseudograd_q": [P, P, L64, P, L64, L64, I, P],
         "nd_qreduce": [P, I, L64, I, P, P],

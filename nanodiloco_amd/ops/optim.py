@@ -88,14 +88,20 @@ def adamw_step(master: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, 
         if max_norm is not None:
             coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
             g = grad * coef
+    _adamw_update_torch(master, g, exp_avg, exp_avg_sq, lr, b1, b2, eps, weight_decay, bc1, bc2)
+    if shadow is not None and shadow.data_ptr() != master.data_ptr():
+        shadow.copy_(master)
+
+
+def _adamw_update_torch(master, g, exp_avg, exp_avg_sq, lr, b1, b2, eps, weight_decay, bc1, bc2) -> None:
+    """The element-wise part of ``adamw_step``'s PyTorch form on an already clipped gradient (also run span by
+    span by ``ops.muon.adamw_step_spans``)."""
     master.mul_(1.0 - lr * weight_decay)
     exp_avg.lerp_(g, 1.0 - b1)
     exp_avg_sq.mul_(b2).addcmul_(g, g, value=1.0 - b2)
     step_size = lr / bc1
     denom = (exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
     master.addcdiv_(exp_avg, denom, value=-step_size)
-    if shadow is not None and shadow.data_ptr() != master.data_ptr():
-        shadow.copy_(master)
 
 
 def pseudograd(sync: torch.Tensor, master: torch.Tensor, out: torch.Tensor) -> None:

@@ -62,6 +62,45 @@ class FlatAdamW:
         self.step_count = int(d["step"])
 
 
+class FlatMuon(FlatAdamW):
+    """Muon ("MuLoCo") on the seven 2-D projection weights of every decoder layer, each HF tensor on its own, and
+    ``FlatAdamW``'s update on everything else (embedding, lm head, norms), under ONE global gradient norm and clip
+    coefficient (ops/muon.py has the algorithm).  The Muon momentum lives in ``exp_avg`` over the Muon spans and
+    ``exp_avg_sq`` stays zero there: no new state vector, and the checkpoint tensors keep their names and sizes.
+    The step is PyTorch code: CPU, or a GPU under the PyTorch backend (``--ops torch``); under the HIP backend it
+    raises (ops/muon.py)."""
+
+    def __init__(self, store: ParamStore, lr: float = 4e-4, momentum: float = 0.95, ns_steps: int = 5,
+                 betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
+                 max_grad_norm: Optional[float] = 1.0, skip_nonfinite: bool = False):
+        super().__init__(store, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite)
+        if ns_steps < 1:
+            raise ValueError("ns_steps must be at least 1")
+        self.momentum = momentum
+        self.ns_steps = ns_steps
+        self.plan = ops.MuonPlan.from_store(store)
+        if not self.plan.groups:
+            raise ValueError("FlatMuon found no decoder projection weights in the store")
+        self.param_groups = [{"lr": lr, "params": list(self.plan.muon_names), "optimizer": "muon"},
+                             {"lr": lr, "params": [n for n in store.names if n not in set(self.plan.muon_names)],
+                              "optimizer": "adamw"}]
+
+    def step(self, lr: Optional[float] = None):
+        lr = self.lr if lr is None else lr
+        for g in self.param_groups:
+            g["lr"] = lr
+        self.step_count += 1
+        ops.join_wgrad()
+        ops.muon_step(self.store.master, self.store.grad, self.exp_avg, self.exp_avg_sq, self.store.shadow, self.plan,
+                      self.step_count, lr, self.momentum, self.ns_steps, self.betas, self.eps, self.weight_decay,
+                      self.max_grad_norm, norm_out=self.last_grad_norm, skip_nonfinite=self.skip_nonfinite,
+                      skipped=self.skipped_steps)
+        self.store.version += 1
+
+    def state_dict(self):
+        return {**super().state_dict(), "momentum": self.momentum, "ns_steps": self.ns_steps}
+
+
 class FlatOuterNesterov:
     def __init__(self, store: ParamStore, lr: float = 0.7, momentum: float = 0.9):
         self.store = store

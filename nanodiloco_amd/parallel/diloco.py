@@ -31,12 +31,12 @@ about which options go together:
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
 from ..models.llama import LlamaForCausalLM
-from ..optim import FlatAdamW, FlatOuterNesterov
+from ..optim import FlatAdamW, FlatMuon, FlatOuterNesterov
 from ..utils.schedule import CosineWarmupSchedule
 from .comm import FlatCommunicator
 from .dist import DistEnv
@@ -98,7 +98,8 @@ class Diloco:
             return ModuleDiloco(model, *args, **kwargs)
         return super().__new__(cls)
 
-    def __init__(self, model: LlamaForCausalLM, inner_optimizer: FlatAdamW, outer_optimizer: FlatOuterNesterov,
+    def __init__(self, model: LlamaForCausalLM, inner_optimizer: Union[FlatAdamW, FlatMuon],
+                 outer_optimizer: FlatOuterNesterov,
                  warmup_steps: int, total_steps: int, inner_steps: int = 100, outer_steps: Optional[int] = None,
                  env: Optional[DistEnv] = None, comm_dtype: torch.dtype = torch.float32, bucket_mb: float = 128.0,
                  overlap: bool = False, offload_snapshot: bool = False, debug_checks: bool = False,

@@ -23,7 +23,7 @@ from .config import LlamaConfig, default_run_config, load_config_from_file, reso
 from .data import build_data, build_eval_data
 from .evaluate import evaluate_model
 from .models import LlamaForCausalLM
-from .optim import FlatAdamW, FlatOuterNesterov
+from .optim import FlatAdamW, FlatMuon, FlatOuterNesterov
 from .parallel.diloco import Diloco
 from .parallel.dist import DistEnv, init_distributed
 from .parallel.inner_ddp import InnerGradSync
@@ -61,6 +61,10 @@ class TrainArgs:
     outer_momentum: float = 0.9
     max_grad_norm: float = 1.0
     weight_decay: float = 0.01
+    inner_optimizer: str = "adamw"  # adamw | muon: Muon ("MuLoCo") on the decoder projection weights, AdamW on the
+                                    # rest (optim.FlatMuon, docs/DESIGN.md "Muon inner optimizer")
+    muon_momentum: float = 0.95
+    muon_ns_steps: int = 5         # Newton-Schulz iterations per Muon step
     comm_dtype: str = "fp32"       # fp32 | bf16 | int8 | int4 (block-quantised outer transport, parallel/diloco.py)
     comm_error_feedback: bool = False  # with int8 | int4: carry what quantisation did not deliver into the next
                                        # outer step (two fp32 residuals per GPU, docs/DESIGN.md "Error feedback")
@@ -234,8 +238,18 @@ class Trainer:
                                       fp8=a.fp8 or a.dtype == "fp8", fp8_wgrad=a.fp8_wgrad,
                                       residual_dtype=_residual_dtype(a.residual_dtype, a.fp8 or a.dtype == "fp8"),
                                       doc_mask=a.doc_mask).init_weights(a.seed)
-        inner = FlatAdamW(self.model.store, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm,
-                          skip_nonfinite=a.skip_nonfinite)
+        if a.inner_optimizer == "muon":
+            if e.device.type == "cuda" and ops.get_backend() != "torch":
+                raise ValueError("--inner-optimizer muon has no HIP kernels yet: on a GPU it needs --ops torch "
+                                 "(docs/DESIGN.md \"Muon inner optimizer\")")
+            inner = FlatMuon(self.model.store, lr=a.lr, momentum=a.muon_momentum, ns_steps=a.muon_ns_steps,
+                             weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm,
+                             skip_nonfinite=a.skip_nonfinite)
+        elif a.inner_optimizer == "adamw":
+            inner = FlatAdamW(self.model.store, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm,
+                              skip_nonfinite=a.skip_nonfinite)
+        else:
+            raise ValueError(f"--inner-optimizer must be adamw or muon, not {a.inner_optimizer!r}")
         outer = FlatOuterNesterov(self.model.store, lr=a.outer_lr, momentum=a.outer_momentum)
         self.diloco = Diloco(self.model, inner, outer, a.warmup_steps, a.total_steps, a.inner_steps, self.outer_steps,
                              env=e, comm_dtype=_comm_dtype(a.comm_dtype, e.device), bucket_mb=a.bucket_mb,

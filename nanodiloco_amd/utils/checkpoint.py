@@ -5,7 +5,10 @@ Directory layout (written only at outer-step boundaries, when all replicas are i
   <dir>/config.json              HF LlamaConfig JSON (+ "architectures": ["LlamaForCausalLM"])
   <dir>/model.safetensors        fp32 master weights, HF key names -> ``LlamaForCausalLM.from_pretrained(dir)``
   <dir>/diloco_state.safetensors outer state shared by all workers: theta_sync, outer momentum
-  <dir>/rank{r}.safetensors      per-rank inner AdamW m/v + data-generator state
+  <dir>/rank{r}.safetensors      per-rank inner AdamW m/v + data-generator state (``--inner-optimizer muon``: the
+                                 same two tensors, the Muon momentum in ``adamw.exp_avg`` over the Muon spans;
+                                 ``trainer_state.json`` then records ``"inner_optimizer": "muon"`` and resume refuses
+                                 a mismatch; a checkpoint without the key is ``adamw``)
   <dir>/trainer_state.json       step counters, schedule, hyper-params, topology (world size, inner_dp,
                                  flat size -- validated on resume), per-rank scalar state
 
@@ -108,6 +111,12 @@ def _load_st(path: str) -> Dict[str, torch.Tensor]:
     return load_file(path)
 
 
+def inner_optimizer_kind(opt) -> str:
+    """``"muon"`` for ``optim.FlatMuon`` (its ``exp_avg`` holds Muon momentum over the Muon spans), else ``"adamw"``."""
+    from ..optim import FlatMuon
+    return "muon" if isinstance(opt, FlatMuon) else "adamw"
+
+
 def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_state: Optional[Dict[str, Any]] = None,
                     extra: Optional[Dict[str, Any]] = None):
     # a collective still in flight (overlapped step, fragment) is waited for and saved as pending, not applied
@@ -152,6 +161,8 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
                  "outer_opt_step": diloco.outer_optimizer.step_count, "scheduler": diloco.scheduler.state_dict(),
                  "world_size": env.world_size, "inner_dp": env.inner_dp, "flat_numel": store.numel,
                  **shared, **(extra or {})}
+        if inner_optimizer_kind(diloco.inner_optimizer) != "adamw":  # an AdamW checkpoint stays as it always was
+            state["inner_optimizer"] = inner_optimizer_kind(diloco.inner_optimizer)
         with open(os.path.join(ckpt_dir, "trainer_state.json"), "w") as f:
             json.dump(state, f, indent=2)
     barrier(env)  # every rank's files are in the staging directory
@@ -185,6 +196,10 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
     with open(os.path.join(ckpt_dir, "trainer_state.json")) as f:
         state = json.load(f)
     store = model.store
+    saved_opt, this_opt = state.get("inner_optimizer", "adamw"), inner_optimizer_kind(diloco.inner_optimizer)
+    if saved_opt != this_opt:
+        raise ValueError(f"checkpoint {ckpt_dir} was written with --inner-optimizer {saved_opt}, this run has "
+                         f"{this_opt}: the optimizer state is not interchangeable, resume with the same optimizer")
     old_world = int(state.get("world_size", env.world_size))
     resized = elastic and old_world != env.world_size
     streamed = state.get("streaming")
