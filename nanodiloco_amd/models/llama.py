@@ -32,16 +32,9 @@ from .. import ops
 from ..config import LlamaConfig
 from ..ops.cross_entropy import LM_KEY
 from .param_store import ParamStore
+from .projections import Bf16Projections, Fp8Projections
 
-_WARNED = set()
 _CONFIG = object()  # generate(): "take it from the model config"
-
-
-def _warn_once(key: str, msg: str) -> None:
-    if key not in _WARNED:
-        _WARNED.add(key)
-        import warnings
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
 
 
 @dataclasses.dataclass
@@ -96,17 +89,11 @@ class LlamaForCausalLM:
         self._qkv_names = [g for g in groups[0::2]]
         self._gu_names = [g for g in groups[1::2]]
         self.layer_hook: Optional[Callable[[int], None]] = None
-        # W^T copies for the input-gradient GEMMs (ops/linear.py), refreshed lazily whenever the
-        # store's weight version moves: key -> [W^T buffer, version it holds, W view]
-        self._wt_cache = {}
         self.training = True
-        self.fp8 = None
-        self._fp8_off = False  # loss_stats: the evaluation forward of an fp8 model runs the bf16 projections
-        if fp8:
-            if compute_dtype != torch.bfloat16 or self.device.type != "cuda":
-                raise ValueError("fp8 needs bf16 compute on an MI355X")
-            from ..ops.fp8 import Fp8Linears
-            self.fp8 = Fp8Linears(self.device, wgrad_fp8=fp8_wgrad)
+        if fp8 and (compute_dtype != torch.bfloat16 or self.device.type != "cuda"):
+            raise ValueError("fp8 needs bf16 compute on an MI355X")
+        self.proj = Fp8Projections(self, fp8_wgrad) if fp8 else Bf16Projections(self)
+        self.fp8 = self.proj.lin if fp8 else None  # the fp8 state (Fp8Linears) behind self.proj
 
     # ------------------------------------------------------------------ init / io
     @torch.no_grad()
@@ -166,109 +153,25 @@ class LlamaForCausalLM:
         return self.store.fused_view(which, names)
 
     # ------------------------------------------------------------------ forward
-    def _wt(self, key, w):
-        """W^T (contiguous) for the dgrad GEMM, or None when the plain layout is used."""
-        if not (self.training and w.is_cuda and w.dtype == torch.bfloat16 and ops.dgrad_transposed_enabled()):
-            return None
-        e = self._wt_cache.get(key)
-        if e is None:
-            e = [torch.empty(w.shape[1], w.shape[0], dtype=w.dtype, device=w.device), -1, w]
-            self._wt_cache[key] = e
-        if e[1] != self.store.version:
-            ops.transpose_into(e[0], w)
-            e[1] = self.store.version
-        return e[0]
-
-    def refresh_transposed(self):
-        """Bring every cached W^T up to the current weights (eagerly, e.g. before a HIP-graph
-        replay, whose captured GEMMs read these buffers but never re-run the version check)."""
-        if not ops.dgrad_transposed_enabled():
-            return
-        for key, e in self._wt_cache.items():
-            if e[1] != self.store.version:
-                ops.transpose_into(e[0], e[2])
-                e[1] = self.store.version
-
-    def _fp8_on(self, key: str) -> bool:
-        if self.fp8 is None or self._fp8_off:
-            return False
-        from ..ops.fp8 import fp8_projection
-        return fp8_projection(key.split(".")[1])
-
-    def _linear(self, key, x, w, gw, x8=None):
-        if self._fp8_on(key):
-            return self.fp8(key, x, w, gw, self.store.version, x8)
-        return ops.linear(x, w, gw, self._wt(key, w))
-
-    def _q8(self, key: str, grad: bool = False):
-        """fp8 inner step: fused-producer quantisation target for projection ``key``'s input
-        (``grad=False``) or output gradient (``grad=True``); None when not applicable."""
-        if not self._fp8_on(key) or not self.training or not torch.is_grad_enabled():
-            return None
-        return self.fp8.dy_target(key) if grad else self.fp8.x_target(key)
+    def refresh_transposed(self):  # bring every cached W^T up to the current weights
+        self.proj.refresh_transposed()
 
     def _layer(self, i, h, y, cos, sin, B, T, next_norm, y8=None, kstart=None, doc=None, cache=None):
-        c = self.config
+        c, proj = self.config, self.proj
         p = f"model.layers.{i}."
-        cdt = self.compute_dtype
-        eps = c.rms_norm_eps
-        qn = self._qkv_names[i]
-        w_qkv = self._fused(qn, "shadow")
-        rope_cols = (c.num_attention_heads + c.num_key_value_heads) * c.head_dim
-        fp8_qkv = self._fp8_on(f"{i}.qkv")
-        wt_qkv = self._wt(f"{i}.qkv", w_qkv) if not fp8_qkv else None
-        if not fp8_qkv and ops.linear_rope_supported(y, w_qkv, wt_qkv, c.head_dim, rope_cols):
-            # own GEMM with RoPE on q|k in its epilogue: the attention skips its rotation pass
-            qkv = ops.linear_rope(y, w_qkv, self._fused(qn, "grad"), wt_qkv, cos, sin, T, c.head_dim, rope_cols)
-            rotated = True
-        elif fp8_qkv and self.fp8.rope_ok(y, w_qkv, c.head_dim, rope_cols):
-            # the same on the own fp8 GEMM (e4m3 operands, RoPE on the dequantised accumulator)
-            qkv = self.fp8.rope(f"{i}.qkv", y, w_qkv, self._fused(qn, "grad"), self.store.version, y8, cos, sin, T,
-                                c.head_dim, rope_cols)
-            rotated = True
-        else:
-            if self.fp8 is not None and not fp8_qkv and not self._fp8_off:
-                _warn_once("qkv", "--fp8-keep-fused rope: the fused bf16 q|k|v + RoPE GEMM cannot run on this "
-                                  "shape; the projection runs as a plain bf16 GEMM + separate RoPE pass (slower "
-                                  "than fp8)")
-            qkv = self._linear(f"{i}.qkv", y, w_qkv, self._fused(qn, "grad"), y8)
-            rotated = False
+        qkv, rotated = proj.qkv(i, y, y8, cos, sin, T)  # rotated: RoPE ran in the GEMM epilogue
         o = ops.attention(qkv, cos, sin, B, T, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
                           inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc)
         if cache is not None:
             # prefill: the HIP path has rotated q|k inside qkv by now (in place, or in the GEMM epilogue); the
             # PyTorch path leaves its input alone and cache_fill rotates k itself
             ops.cache_fill(cache, i, qkv, B, T, cos, sin, rotated=rotated or ops._ext.use_hip(qkv))
-        a = self._linear(f"{i}.o", o, self._w(p + "self_attn.o_proj.weight"), self._g(p + "self_attn.o_proj.weight"))
-        q_gu = self._q8(f"{i}.gu")
+        a = proj.o(i, o)
+        q_gu = proj.x_target(f"{i}.gu")
         y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"),
-                               self._g(p + "post_attention_layernorm.weight"), eps, cdt,
-                               q8=q_gu, q8_bwd=self._q8(f"{i}.o", grad=True))
-        gn = self._gu_names[i]
-        w_gu = self._fused(gn, "shadow")
-        w_dn = self._w(p + "mlp.down_proj.weight")
-        if not self._fp8_on(f"{i}.gu"):
-            wt_gu, wt_dn = self._wt(f"{i}.gu", w_gu), self._wt(f"{i}.down", w_dn)
-            if ops.mlp_fused_supported(y, w_gu, wt_gu, w_dn, wt_dn):
-                # own GEMMs with SwiGLU in the gate|up epilogue and its backward in the down dgrad's
-                m = ops.mlp_fused(y, w_gu, self._fused(gn, "grad"), wt_gu, w_dn,
-                                  self._g(p + "mlp.down_proj.weight"), wt_dn)
-                return m, h
-            if self.fp8 is not None and not self._fp8_off:
-                _warn_once("mlp", "--fp8-keep-fused mlp: the fused bf16 SwiGLU GEMMs cannot run on this shape; "
-                                  "the MLP runs as plain bf16 GEMMs + separate SwiGLU passes (slower than fp8)")
-        elif self.fp8.mlp_ok(y, w_gu, w_dn):
-            # the same fusion on the own fp8 GEMMs
-            m = self.fp8.mlp(f"{i}.gu", f"{i}.down", y, w_gu, w_dn, self._fused(gn, "grad"),
-                             self._g(p + "mlp.down_proj.weight"), self.store.version,
-                             q_gu.out if q_gu is not None else None)
-            return m, h
-        q_down = self._q8(f"{i}.down")
-        gu = self._linear(f"{i}.gu", y, w_gu, self._fused(gn, "grad"), q_gu.out if q_gu is not None else None)
-        act = ops.swiglu(gu, q8=q_down, q8_bwd=self._q8(f"{i}.gu", grad=True))
-        m = self._linear(f"{i}.down", act, w_dn, self._g(p + "mlp.down_proj.weight"),
-                         q_down.out if q_down is not None else None)
-        return m, h
+                               self._g(p + "post_attention_layernorm.weight"), c.rms_norm_eps, self.compute_dtype,
+                               q8=q_gu, q8_bwd=proj.dy_target(f"{i}.o"))
+        return proj.mlp(i, y, q_gu), h
 
     def hidden_states(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                       cache=None) -> torch.Tensor:
@@ -294,7 +197,7 @@ class LlamaForCausalLM:
             # layer 0's last gradient (its input_layernorm weight) is written by the backward of the
             # norm below; the hook node on the norm's INPUT runs right after that backward
             h = _GradHook.apply(h, hook, 0)
-        q = self._q8("0.qkv")
+        q = self.proj.x_target("0.qkv")
         # (y, h): the embedding output feeds both the first norm and the residual stream; rmsnorm_res
         # fuses the two gradient contributions inside the norm's backward kernel
         y, h = ops.rmsnorm_res(h, self._m("model.layers.0.input_layernorm.weight"),
@@ -312,12 +215,10 @@ class LlamaForCausalLM:
                 # layer i+1's gradients are final once the backward of the add+norm that produces its
                 # input (and owns its input_layernorm weight) has run: hook that norm's input
                 m = _GradHook.apply(m, hook, i + 1)
-            q = self._q8(f"{i + 1}.qkv") if i + 1 < L else self._q8(LM_KEY)
+            q = self.proj.x_target(f"{i + 1}.qkv" if i + 1 < L else LM_KEY)
             y, h = ops.add_rmsnorm(h, m, self._m(nxt), self._g(nxt), eps, cdt, q8=q,
-                                   q8_bwd=self._q8(f"{i}.down", grad=True))
+                                   q8_bwd=self.proj.dy_target(f"{i}.down"))
             y8 = q.out if q is not None else None
-        # the final norm's fused e4m3 copy of y feeds the fp8 lm head (ops/cross_entropy.py); None otherwise
-        self._lm_y8 = y8 if L > 0 else None
         return y
 
     def forward(self, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None, attention_mask=None,
@@ -327,22 +228,15 @@ class LlamaForCausalLM:
         follows HF too: pad keys are masked for every real token (left or right padding; pad positions
         should carry label -100, as the HF data path sets them)."""
         y = self.hidden_states(input_ids, attention_mask)
-        lm = "lm_head.weight" if not self.config.tie_word_embeddings else "model.embed_tokens.weight"
         out = CausalLMOutput()
         if labels is not None or targets is not None:
             if targets is None:
                 targets = ops.reference.shift_labels(labels, ops.IGNORE_INDEX)
-            w_lm = self._w(lm)
-            f8 = None
-            if self._fp8_on(LM_KEY) and self.training and torch.is_grad_enabled():
-                f8 = (self.fp8, self.store.version, getattr(self, "_lm_y8", None))
-            out.loss = ops.lm_head_ce(y, w_lm, self._g(lm), targets.reshape(-1), loss_scale,
-                                      wt=self._wt("lm_head", w_lm) if f8 is None else None, f8=f8)
-            self._lm_y8 = None
+            out.loss = self.proj.lm_head_ce(y, targets.reshape(-1), loss_scale)
         if return_logits or (labels is None and targets is None):
             with torch.no_grad():
                 B, T = input_ids.shape
-                out.logits = ops.mm_nt(y.detach(), self._w(lm)).float().view(B, T, -1)
+                out.logits = ops.mm_nt(y.detach(), self._w(self._lm_name())).float().view(B, T, -1)
         return out
 
     @torch.no_grad()
@@ -359,15 +253,10 @@ class LlamaForCausalLM:
         (amax partials, history, scales, first-use flags) nor the ``Fp8Weight`` caches are read or written, the
         next training step is bitwise what it would have been without the evaluation, and the number does not
         depend on the scaling history."""
-        was_training, was_off, lm_y8 = self.training, self._fp8_off, getattr(self, "_lm_y8", None)
-        self.training, self._fp8_off = False, True
-        try:
+        with self._inference():
             y = self.hidden_states(input_ids, attention_mask)
-            lm = "lm_head.weight" if not self.config.tie_word_embeddings else "model.embed_tokens.weight"
             targets = ops.reference.shift_labels(labels, ops.IGNORE_INDEX).reshape(-1)
-            row_loss, row_hit = ops.lm_head_loss(y, self._w(lm), targets)
-        finally:
-            self.training, self._fp8_off, self._lm_y8 = was_training, was_off, lm_y8
+            row_loss, row_hit = ops.lm_head_loss(y, self._w(self._lm_name()), targets)
         return torch.stack([row_loss.sum(dtype=torch.float64), (targets != ops.IGNORE_INDEX).sum().double(),
                             row_hit.sum().double()])
 
@@ -377,15 +266,15 @@ class LlamaForCausalLM:
 
     @contextlib.contextmanager
     def _inference(self):
-        """What ``loss_stats`` does: gradient views off, and for an fp8 model the bf16 projections on the bf16 shadow
-        weights, so that nothing of the delayed-scaling state is read or written; everything restored on exit."""
-        saved = (self.training, self._fp8_off, getattr(self, "_lm_y8", None))
-        self.training, self._fp8_off = False, True
+        """Evaluation and generation: gradient views off, and for an fp8 model its held bf16 projections on the bf16
+        shadow weights, so that nothing of the delayed-scaling state is read or written; everything restored on exit."""
+        saved = (self.training, self.proj)
+        self.training, self.proj = False, self.proj.bf16
         try:
             with torch.no_grad():
                 yield
         finally:
-            self.training, self._fp8_off, self._lm_y8 = saved
+            self.training, self.proj = saved
 
     def new_cache(self, batch: int, s_max: int):
         return ops.KVCache(self.config, batch, s_max, self.device, self.compute_dtype)

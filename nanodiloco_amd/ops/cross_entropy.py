@@ -60,7 +60,7 @@ def _chunks(n: int, V: int, elem: int, chunk_rows: int):
 
 class LMHeadCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None):
+    def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None, version=0, y8=None):
         n, d = y.shape
         V = w.shape[0]
         targets = targets.reshape(-1)
@@ -71,29 +71,22 @@ class LMHeadCEFn(torch.autograd.Function):
         loss_sum = torch.zeros(1, dtype=torch.float32, device=y.device)
         hip = _ext.use_hip(y)
         det = deterministic()
-        q = None
+        q = r = None
         if f8 is not None and hip:
-            from .fp8 import E4M3, E5M2, _wgrad_f8, cast
+            from .fp8 import E5M2, issue_wgrad_f8
             from .gemm import gemm_pp_f8, pp_f8_supported
-            lin, version, y8 = f8
-            kx, kdy = lin._slots(LM_KEY)
-            r = lin.recipe
-            if y8 is None or y8.shape != y.shape:
-                y8 = r.quantize(y, kx, E4M3)
-            wq = lin.weights[LM_KEY].get(w, version)
-            if pp_f8_supported(y8, wq.w8) and V % 128 == 0:
-                q = (r, kx, kdy, y8, wq)
+            kx, kdy, y8, wq = f8.operands(LM_KEY, y, w, version, y8)
+            q = r = f8.recipe if pp_f8_supported(y8, wq.w8) and V % 128 == 0 else None
         for s, e in _chunks(n, V, y.element_size() if hip else 4, chunk_rows):
             yc, tc = y[s:e], targets[s:e]
             if hip:
                 if q is not None:  # fp8: e4m3 x e4m3 on the own fp8 ping-pong kernel
-                    r, kx, kdy, y8, wq = q
                     logits = gemm_pp_f8(y8[s:e], wq.w8, r.inv[kx:kx + 1], wq.inv)
                 else:  # the selected plain projection GEMM (ops/linear.py proj_gemm: hipBLASLt by default)
                     logits = mm_nt(yc, w)
                 rows = torch.empty(e - s, dtype=torch.float32, device=y.device) if det else None
                 dl8 = None
-                t8 = q[0].target(q[2], E5M2) if q is not None else None
+                t8 = r.target(kdy, E5M2) if q is not None else None
                 if t8 is not None:
                     # fp8: the CE kernel writes the e5m2 dlogits itself (no bf16 dlogits, no separate cast)
                     q8 = t8.alloc((e - s, V), y.device)
@@ -127,13 +120,10 @@ class LMHeadCEFn(torch.autograd.Function):
                 dl = p.to(y.dtype)
             if q is not None:
                 # e5m2 dlogits (one cast; delayed scaling of slot kdy), then both gradient GEMMs in fp8
-                r, kx, kdy, y8, wq = q
                 if dl8 is None:
-                    r._first_use(dl, kdy)
-                    dl8 = cast(dl, r.scale[kdy:kdy + 1], E5M2, r.amax[kdy])
+                    dl8 = r.quantize(dl, kdy, E5M2)
                 gemm_pp_f8(dl8, wq.wT8, r.inv[kdy:kdy + 1], wq.inv, out=dy[s:e])
-                if gw is not None:
-                    _wgrad_f8(gw, dl8, y8[s:e], r.inv[kdy:kdy + 1], r.inv[kx:kx + 1], dl)
+                issue_wgrad_f8(gw, dl8, y8[s:e], r.inv[kdy:kdy + 1], r.inv[kx:kx + 1], dl)
                 continue
             # dy rows written in place (a row slice of a contiguous tensor); with wt = W^T the GEMM
             # has the faster K-contiguous operand layout (ops/linear.py)
@@ -153,17 +143,17 @@ class LMHeadCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dy,) = ctx.saved_tensors
-        return dy * g.to(dy.dtype), None, None, None, None, None, None, None
+        return (dy * g.to(dy.dtype),) + (None,) * 9
 
 
 LM_KEY = "x.lm"  # the lm head's slot pair / weight cache in Fp8Linears (ops/fp8.py fp8_projection("lm"))
 
 
-def lm_head_ce(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torch.Tensor,
-               loss_scale: float = 1.0, chunk_rows: int = 0, wt: torch.Tensor = None, f8=None) -> torch.Tensor:
-    """``wt``: optional W^T copy [d, V] for the input-gradient GEMM (see ops/linear.py).  ``f8``:
-    (Fp8Linears, weight version, fused e4m3 copy of y or None) for the fp8 lm head."""
-    return LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8)
+def lm_head_ce(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torch.Tensor, loss_scale: float = 1.0,
+               chunk_rows: int = 0, wt: torch.Tensor = None, f8=None, version: int = 0, y8=None) -> torch.Tensor:
+    """``wt``: optional W^T copy [d, V] for the input-gradient GEMM (see ops/linear.py).  ``f8``: the model's
+    ``Fp8Linears`` for the fp8 lm head, with the weight ``version`` and ``y8``, the fused e4m3 copy of y if any."""
+    return LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8, int(version), y8)
 
 
 @torch.no_grad()

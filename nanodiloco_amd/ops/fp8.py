@@ -34,20 +34,17 @@ import torch
 
 from . import _ext
 from .gemm import (gemm_pp_dswiglu_f8, gemm_pp_dswiglu_f8q, gemm_pp_f8, gemm_pp_rope_f8,
-                   gemm_pp_swiglu_f8, gemm_pp_swiglu_f8q, pp_f8_supported, wgrad, wgrad_f8, wgrad_f8_supported,
-                   wgrad_supported)
+                   gemm_pp_swiglu_f8, gemm_pp_swiglu_f8q, pp_f8_supported, wgrad_f8, wgrad_f8_supported)
+from .linear import issue_wgrad, library_gemm_fence, wgrad_bf16
 
 E4M3, E5M2 = 0, 1
 FMAX = {E4M3: 448.0, E5M2: 57344.0}
 TORCH_DT = {E4M3: torch.float8_e4m3fn, E5M2: torch.float8_e5m2}
-
-
 AMAX_PARTS = 64
 _FUSED = {"enabled": True}
 # "pp" (default): the ping-pong kernel on fp8 operands (csrc/gemm_pp.hip F8, 16x16x128 f8f6f4 MFMA), which
-# also carries the fused RoPE / SwiGLU epilogues; "hipblaslt": torch._scaled_mm (A/B).  (The round-2
-# one-wave-per-SIMD fp8 kernel, 0.95x hipBLASLt, was removed in round 5.)  Shapes the own kernels do not take fall back to
-# torch._scaled_mm.
+# also carries the fused RoPE / SwiGLU epilogues; "hipblaslt": torch._scaled_mm (A/B), which also takes the
+# shapes the own kernels do not.
 _GEMM = {"backend": "pp"}
 # fp8 projections with their fused epilogues on the own fp8 GEMM: q|k|v + RoPE, gate|up + SwiGLU and the
 # down input gradient + SwiGLU backward (backend "pp" only)
@@ -87,8 +84,7 @@ def mm8(a8: torch.Tensor, b8: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor) 
     be = _GEMM["backend"]
     if (be == "pp" or (be == "auto" and _own_plain(a8, b8))) and pp_f8_supported(a8, b8):
         return gemm_pp_f8(a8, b8, sa, sb)
-    from .linear import library_gemm_fence  # hipBLASLt stream-K must not co-run with side-stream wgrads
-    library_gemm_fence(a8.device if a8.is_cuda else None)
+    library_gemm_fence(a8.device if a8.is_cuda else None)  # hipBLASLt stream-K must not co-run with side-stream wgrads
     return torch._scaled_mm(a8, b8.t(), sa, sb, out_dtype=torch.bfloat16)
 
 
@@ -253,14 +249,6 @@ class Fp8Recipe:
         scaled from the tensor's own amax, which only the separate cast can do)."""
         return QuantTarget(self, k, fmt) if (self.ready[k] and _FUSED["enabled"]) else None
 
-    def quantize_t(self, x: torch.Tensor, k: int, fmt: int, want_plain: bool = True):
-        """(x8, x8^T) with the slot's scale (falls back to a separate transpose off the fast shapes)."""
-        self._first_use(x, k)
-        if _t_ok(x):
-            return cast_t(x, self.scale[k:k + 1], fmt, self.amax[k], want_plain)
-        q = cast(x, self.scale[k:k + 1], fmt, self.amax[k])
-        return q, q.t().contiguous()
-
     @torch.no_grad()
     def update(self):
         """Roll the amax history and refresh every scale (call once per inner step)."""
@@ -305,98 +293,70 @@ class Fp8Weight:
         return self
 
 
+def _forward(ctx, x, gw, wq: "Fp8Weight", recipe: Fp8Recipe, kx: int, kdy: int, wgrad_fp8: bool, x8, gemm, *epi):
+    """The forward of a single fp8 projection: e4m3 x (the producer's fused copy ``x8`` or a cast) -> ``gemm``."""
+    if x8 is None or x8.shape != x.shape:
+        x8 = recipe.quantize(x, kx, E4M3)
+    # fp8 weight gradient: keep x8 (half the bytes of x) for dW = dy8^T x8
+    ctx.save_for_backward(x8 if wgrad_fp8 else x)
+    inv_x = recipe.inv[kx:kx + 1]
+    ctx.gw, ctx.wq, ctx.recipe, ctx.kdy, ctx.inv_x, ctx.wgrad_fp8 = gw, wq, recipe, kdy, inv_x, wgrad_fp8
+    ctx.nones = 8 + len(epi)  # forward arguments after x
+    return gemm(x8, wq.w8, inv_x, wq.inv, *epi)
+
+
 class Fp8LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, gw, wq: Fp8Weight, recipe: Fp8Recipe, kx: int, kdy: int, wgrad_fp8: bool, x8=None):
-        if x8 is None or x8.shape != x.shape:
-            x8 = recipe.quantize(x, kx, E4M3)
-        # fp8 weight gradient: keep x8 (half the bytes of x) for dW = dy8^T x8
-        ctx.save_for_backward(x8 if wgrad_fp8 else x)
-        inv_x = recipe.inv[kx:kx + 1]
-        y = mm8(x8, wq.w8, inv_x, wq.inv)
-        ctx.gw, ctx.wq, ctx.recipe, ctx.kdy, ctx.inv_x, ctx.wgrad_fp8 = gw, wq, recipe, kdy, inv_x, wgrad_fp8
-        return y
+        return _forward(ctx, x, gw, wq, recipe, kx, kdy, wgrad_fp8, x8, mm8)
 
     @staticmethod
     def backward(ctx, dy):
-        (xs,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        r, k = ctx.recipe, ctx.kdy
-        dy8 = _dy8(r, k, dy)
-        inv_dy = r.inv[k:k + 1]
-        dx = mm8(dy8, ctx.wq.wT8, inv_dy, ctx.wq.inv)
-        if ctx.wgrad_fp8:
-            _wgrad_f8(ctx.gw, dy8, xs, inv_dy, ctx.inv_x, dy)
-        else:
-            _wgrad_bf16(ctx.gw, dy, xs)
-        return dx, None, None, None, None, None, None, None, None
+        return (_backward(ctx.recipe, ctx.kdy, dy.contiguous(), ctx.wq, ctx.gw, ctx.saved_tensors[0], ctx.inv_x,
+                          ctx.wgrad_fp8),) + (None,) * ctx.nones
 
 
-def _wgrad_bf16(gw, dy, x):
-    if gw is None:
-        return
-    from .linear import _wgrad  # side stream when the weight-gradient overlap is on
-    _wgrad(gw, dy, x)
-
-
-def _wgrad_f8(gw, dy8, x8, inv_dy, inv_x, dy=None):
+def issue_wgrad_f8(gw, dy8, x8, inv_dy, inv_x, dy=None):
     """gw += dy^T x from the fp8 operands (own kernel, csrc/gemm_wgrad.hip wgrad8_pp_kernel); shapes it does
     not take fall back to the bf16 kernel on the dequantised operands (``dy``: the bf16 gradient if kept).
-    With the weight-gradient overlap on (ops/linear.py ``set_wgrad_overlap``) it runs on the side stream like
-    the bf16 weight gradients: joined before every library GEMM and before the optimizer."""
+    Like the bf16 weight gradients it goes through ``issue_wgrad`` (side stream when the overlap is on)."""
     if gw is None:
         return
     if wgrad_f8_supported(gw, dy8, x8):
-        from .linear import _OVERLAP, _side_stream
-        if _OVERLAP["enabled"] and gw.is_cuda:
-            cur = torch.cuda.current_stream(gw.device)
-            side = _side_stream(gw.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                wgrad_f8(gw, dy8, x8, inv_dy, inv_x)
-            _OVERLAP["keep"].append((dy8, x8))
-            _OVERLAP["pending"].add(side.device.index)
-        else:
-            wgrad_f8(gw, dy8, x8, inv_dy, inv_x)
+        issue_wgrad(gw.device, lambda: wgrad_f8(gw, dy8, x8, inv_dy, inv_x), (dy8, x8))
     else:
         if dy is None:
             dy = (dy8.float() * inv_dy).to(torch.bfloat16)
-        _wgrad_bf16(gw, dy, (x8.float() * inv_x).to(dy.dtype))
+        wgrad_bf16(gw, dy, (x8.float() * inv_x).to(dy.dtype))
 
 
-def _dy8(r: Fp8Recipe, k: int, dy: torch.Tensor) -> torch.Tensor:
-    dy8 = r.take_stashed(k, dy)  # written by a fused producer (RMSNorm backward)
-    return dy8 if dy8 is not None else r.quantize(dy, k, E5M2)
+def _backward(r: Fp8Recipe, kdy: int, dy, wq: "Fp8Weight", gw, xs, inv_x, wgrad_fp8: bool, dy8=None, dgrad=None):
+    """The backward of every fp8 projection: e5m2 dy -> input-gradient GEMM -> fp8 or bf16 weight gradient.
+    ``dy8``: the e5m2 copy if the caller has it; else a fused producer's stashed copy (RMSNorm backward) or a cast.
+    ``dgrad(dy8, inv_dy)``: the input-gradient GEMM where it is not the plain dy8 . W8; its result is returned.
+    ``xs``: the saved forward operand, x8 with ``wgrad_fp8`` and x otherwise."""
+    if dy8 is None:
+        dy8 = r.take_stashed(kdy, dy)
+        if dy8 is None:
+            dy8 = r.quantize(dy, kdy, E5M2)
+    inv_dy = r.inv[kdy:kdy + 1]
+    dx = dgrad(dy8, inv_dy) if dgrad is not None else mm8(dy8, wq.wT8, inv_dy, wq.inv)
+    if wgrad_fp8:
+        issue_wgrad_f8(gw, dy8, xs, inv_dy, inv_x, dy)
+    else:
+        wgrad_bf16(gw, dy, xs)
+    return dx
 
 
-class Fp8RopeFn(torch.autograd.Function):
+class Fp8RopeFn(Fp8LinearFn):
     """fp8 q|k|v projection with RoPE in the epilogue of the own fp8 GEMM (bf16 output, rotated q|k).
     The attention backward returns the gradient of the UN-rotated projection, so the backward is the
-    plain fp8 projection backward (e5m2 dy x e4m3 W^T) plus the bf16 weight gradient."""
+    plain fp8 projection backward, inherited."""
 
     @staticmethod
     def forward(ctx, x, w, gw, wq: "Fp8Weight", recipe: Fp8Recipe, kx: int, kdy: int, x8, cos, sin, T: int, hd: int,
                 rope_cols: int, wgrad_fp8: bool):
-        if x8 is None or x8.shape != x.shape:
-            x8 = recipe.quantize(x, kx, E4M3)
-        inv_x = recipe.inv[kx:kx + 1]
-        y = gemm_pp_rope_f8(x8, wq.w8, inv_x, wq.inv, cos, sin, T, hd, rope_cols)
-        ctx.save_for_backward(x8 if wgrad_fp8 else x)
-        ctx.gw, ctx.wq, ctx.recipe, ctx.kdy, ctx.inv_x, ctx.wgrad_fp8 = gw, wq, recipe, kdy, inv_x, wgrad_fp8
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (xs,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        r, k = ctx.recipe, ctx.kdy
-        dy8 = _dy8(r, k, dy)
-        dx = mm8(dy8, ctx.wq.wT8, r.inv[k:k + 1], ctx.wq.inv)
-        if ctx.wgrad_fp8:
-            _wgrad_f8(ctx.gw, dy8, xs, r.inv[k:k + 1], ctx.inv_x, dy)
-        else:
-            _wgrad_bf16(ctx.gw, dy, xs)
-        return (dx,) + (None,) * 13
+        return _forward(ctx, x, gw, wq, recipe, kx, kdy, wgrad_fp8, x8, gemm_pp_rope_f8, cos, sin, T, hd, rope_cols)
 
 
 class Fp8MLPFn(torch.autograd.Function):
@@ -433,29 +393,20 @@ class Fp8MLPFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dm):
         ys, gu, acts = ctx.saved_tensors
-        gw_gu, gw_dn = ctx.gw
-        wq_gu, wq_dn = ctx.wq
-        r = ctx.recipe
+        (gw_gu, gw_dn), (wq_gu, wq_dn), r = ctx.gw, ctx.wq, ctx.recipe
         k_gx, k_gdy, k_dx, k_ddy = ctx.ks
         dm = dm.contiguous()
-        dm8 = _dy8(r, k_ddy, dm)
-        if ctx.wgrad_fp8 and r.ready[k_gdy] and _FUSED["enabled"] and dm.shape[0] % 128 == 0:
-            # only the e5m2 d(gate|up) is consumed (dgrad and fp8 wgrad): the epilogue writes it directly
-            dgu8 = gemm_pp_dswiglu_f8q(dm8, wq_dn.wT8, r.inv[k_ddy:k_ddy + 1], wq_dn.inv, gu,
-                                       r.scale[k_gdy:k_gdy + 1], r.amax[k_gdy])
-            dgu = None
-        else:
-            dgu = gemm_pp_dswiglu_f8(dm8, wq_dn.wT8, r.inv[k_ddy:k_ddy + 1], wq_dn.inv, gu)
-            dgu8 = r.quantize(dgu, k_gdy, E5M2)
-        if ctx.wgrad_fp8:
-            _wgrad_f8(gw_dn, dm8, acts, r.inv[k_ddy:k_ddy + 1], r.inv[k_dx:k_dx + 1], dm)
-        else:
-            _wgrad_bf16(gw_dn, dm, acts)
-        dy = mm8(dgu8, wq_gu.wT8, r.inv[k_gdy:k_gdy + 1], wq_gu.inv)
-        if ctx.wgrad_fp8:
-            _wgrad_f8(gw_gu, dgu8, ys, r.inv[k_gdy:k_gdy + 1], r.inv[k_gx:k_gx + 1], dgu)
-        else:
-            _wgrad_bf16(gw_gu, dgu, ys)
+
+        def down_dgrad(dm8, inv_dm):  # the down input gradient with the SwiGLU backward in its epilogue
+            if ctx.wgrad_fp8 and r.ready[k_gdy] and _FUSED["enabled"] and dm.shape[0] % 128 == 0:
+                # only the e5m2 d(gate|up) is consumed (dgrad and fp8 wgrad): the epilogue writes it directly
+                return None, gemm_pp_dswiglu_f8q(dm8, wq_dn.wT8, inv_dm, wq_dn.inv, gu, r.scale[k_gdy:k_gdy + 1],
+                                                 r.amax[k_gdy])
+            dgu = gemm_pp_dswiglu_f8(dm8, wq_dn.wT8, inv_dm, wq_dn.inv, gu)
+            return dgu, r.quantize(dgu, k_gdy, E5M2)
+
+        dgu, dgu8 = _backward(r, k_ddy, dm, wq_dn, gw_dn, acts, r.inv[k_dx:k_dx + 1], ctx.wgrad_fp8, dgrad=down_dgrad)
+        dy = _backward(r, k_gdy, dgu, wq_gu, gw_gu, ys, r.inv[k_gx:k_gx + 1], ctx.wgrad_fp8, dy8=dgu8)
         return (dy,) + (None,) * 10
 
 
@@ -474,24 +425,21 @@ class Fp8Linears:
             self.weights[key] = Fp8Weight()
         return self.slots[key]
 
-    def x_target(self, key: str) -> Optional[QuantTarget]:
-        """Fused-producer target for the projection ``key``'s input (e4m3)."""
-        return self.recipe.target(self._slots(key)[0], E4M3)
+    def operands(self, key: str, x: torch.Tensor, w: torch.Tensor, version: int, x8: Optional[torch.Tensor] = None):
+        """(x slot, dy slot, e4m3 x, Fp8Weight of ``w``) for the lm head, which runs its GEMMs itself."""
+        kx, kdy = self._slots(key)
+        if x8 is None or x8.shape != x.shape:
+            x8 = self.recipe.quantize(x, kx, E4M3)
+        return kx, kdy, x8, self.weights[key].get(w, version)
 
-    def dy_target(self, key: str) -> Optional[QuantTarget]:
-        """Fused-producer target for the gradient of projection ``key``'s output (e5m2)."""
-        return self.recipe.target(self._slots(key)[1], E5M2)
+    def target(self, key: str, grad: bool = False) -> Optional[QuantTarget]:
+        """Fused-producer target for projection ``key``'s input (e4m3), or the gradient of its output (e5m2)."""
+        return self.recipe.target(self._slots(key)[int(grad)], E5M2 if grad else E4M3)
 
     def rope_ok(self, x: torch.Tensor, w: torch.Tensor, hd: int, rope_cols: int) -> bool:
         """Can the q|k|v projection run as fp8 GEMM + fused RoPE (own kernel)."""
         return (fp8_fused_epilogues() and x.is_cuda and x.dim() == 2 and x.stride(1) == 1
                 and x.shape[1] % 128 == 0 and w.shape[0] % 8 == 0 and hd in (32, 64) and rope_cols % 64 == 0)
-
-    def rope(self, key: str, x, w, gw, version: int, x8, cos, sin, T: int, hd: int, rope_cols: int):
-        kx, kdy = self._slots(key)
-        wq = self.weights[key].get(w, version)
-        return Fp8RopeFn.apply(x, w, gw, wq, self.recipe, kx, kdy, x8, cos, sin, int(T), int(hd), int(rope_cols),
-                               self.wgrad_fp8)
 
     def mlp_ok(self, y: torch.Tensor, w_gu: torch.Tensor, w_dn: torch.Tensor) -> bool:
         """Can the MLP run as fp8 GEMMs with the fused SwiGLU forward / backward epilogues."""
@@ -500,15 +448,15 @@ class Fp8Linears:
                 and y.shape[1] % 128 == 0 and F % 128 == 0 and w_dn.shape[1] == F and w_dn.shape[0] % 128 == 0)
 
     def mlp(self, kgu: str, kdn: str, y, w_gu, w_dn, gw_gu, gw_dn, version: int, y8=None):
-        k_gx, k_gdy = self._slots(kgu)
-        k_dx, k_ddy = self._slots(kdn)
-        wq_gu = self.weights[kgu].get(w_gu, version)
-        wq_dn = self.weights[kdn].get(w_dn, version)
-        return Fp8MLPFn.apply(y, w_gu, w_dn, gw_gu, gw_dn, wq_gu, wq_dn, self.recipe, (k_gx, k_gdy, k_dx, k_ddy), y8,
-                              self.wgrad_fp8)
+        ks = self._slots(kgu) + self._slots(kdn)  # (gu.x, gu.dy, down.x, down.dy)
+        wq_gu, wq_dn = self.weights[kgu].get(w_gu, version), self.weights[kdn].get(w_dn, version)
+        return Fp8MLPFn.apply(y, w_gu, w_dn, gw_gu, gw_dn, wq_gu, wq_dn, self.recipe, ks, y8, self.wgrad_fp8)
 
     def __call__(self, key: str, x: torch.Tensor, w: torch.Tensor, gw: Optional[torch.Tensor], version: int,
-                 x8: Optional[torch.Tensor] = None):
+                 x8: Optional[torch.Tensor] = None, rope=None):
+        """``rope`` = (cos, sin, T, hd, rope_cols): q|k|v with RoPE in the GEMM epilogue (where ``rope_ok``)."""
         kx, kdy = self._slots(key)
         wq = self.weights[key].get(w, version)
+        if rope is not None:
+            return Fp8RopeFn.apply(x, w, gw, wq, self.recipe, kx, kdy, x8, *rope, self.wgrad_fp8)
         return Fp8LinearFn.apply(x, w, gw, wq, self.recipe, kx, kdy, self.wgrad_fp8, x8)

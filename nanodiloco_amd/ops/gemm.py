@@ -73,7 +73,8 @@ def gemm_pp_rope(a, b, cos, sin, T: int, hd: int, rope_cols: int, out=None) -> t
 
 
 def gemm_pp_swiglu(a, w_gu, gu_out=None, act_out=None):
-    """(gu, act): gu = a . w_gu^T ([M, 2F]), act = silu(gu[:, :F]) * gu[:, F:] ([M, F])."""
+    """(gu, act): act [M, F] = silu(gate) * up of [gate | up] = a . w_gu^T; gu [M, 2F], saved for the matching
+    ``gemm_pp_dswiglu*`` only, holds [gate | up], or [A | B] = [d act/d gate | d act/d up] when ``mlp_coef()``."""
     M, K = a.shape
     F = w_gu.shape[0] // 2
     gu = gu_out if gu_out is not None else torch.empty(M, 2 * F, dtype=a.dtype, device=a.device)
@@ -85,7 +86,8 @@ def gemm_pp_swiglu(a, w_gu, gu_out=None, act_out=None):
 
 
 def gemm_pp_dswiglu(dy, w_down_t, gu, dgu_out=None):
-    """d(gate|up) [M, 2F] of act = silu(gate) * up, where d(act) = dy . w_down_t^T (never stored)."""
+    """d(gate|up) [M, 2F] from d(act) = dy . w_down_t^T (never stored) and ``gu`` as ``gemm_pp_swiglu*`` saved it
+    under the same ``mlp_coef()`` ([gate | up] or [A | B])."""
     M, K = dy.shape
     F = w_down_t.shape[0]
     dgu = dgu_out if dgu_out is not None else torch.empty_like(gu)
@@ -132,7 +134,7 @@ def gemm_pp_rope_f8(a, b, sa, sb, cos, sin, T: int, hd: int, rope_cols: int, out
 
 
 def gemm_pp_swiglu_f8(a, w_gu, sa, sb, gu_out=None, act_out=None):
-    """fp8 gate|up projection (a, w_gu e4m3) + SwiGLU: (gu [M, 2F], act [M, F]) in bf16."""
+    """``gemm_pp_swiglu`` on fp8 operands (a, w_gu e4m3): (saved gu [M, 2F], act [M, F]) in bf16."""
     M, K = a.shape
     F = w_gu.shape[0] // 2
     gu = gu_out if gu_out is not None else torch.empty(M, 2 * F, dtype=torch.bfloat16, device=a.device)
@@ -146,7 +148,7 @@ def gemm_pp_swiglu_f8(a, w_gu, sa, sb, gu_out=None, act_out=None):
 
 def gemm_pp_dswiglu_f8(dy, w_down_t, sa, sb, gu, dgu_out=None):
     """fp8 down-projection input gradient (dy e5m2 / e4m3, w_down_t e4m3) fused with the SwiGLU backward:
-    d(gate|up) [M, 2F] bf16."""
+    d(gate|up) [M, 2F] bf16 from the saved ``gu`` ([gate | up] or [A | B], as ``gemm_pp_dswiglu``)."""
     M, K = dy.shape
     F = w_down_t.shape[0]
     dgu = dgu_out if dgu_out is not None else torch.empty_like(gu)

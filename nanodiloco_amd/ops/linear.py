@@ -66,7 +66,7 @@ def wgrad_overlap_enabled() -> bool:
     return _OVERLAP["enabled"]
 
 
-def _side_stream(device: torch.device) -> torch.cuda.Stream:
+def side_stream(device: torch.device) -> torch.cuda.Stream:
     key = device.index if device.index is not None else torch.cuda.current_device()
     s = _OVERLAP["streams"].get(key)
     if s is None:
@@ -96,14 +96,22 @@ def library_gemm_fence(device=None) -> None:
         join_wgrad(device)
 
 
-def _wgrad_on_side_stream(gw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor) -> None:
-    cur = torch.cuda.current_stream(gw.device)
-    side = _side_stream(gw.device)
-    side.wait_stream(cur)
+def issue_wgrad(device: torch.device, launch, keep) -> None:
+    """``launch()`` (weight-gradient GEMMs): on the side stream forked from the current one when the overlap is on
+    and ``device`` is a GPU, with ``keep`` (its operands) referenced until ``join_wgrad``; in place otherwise."""
+    if not (_OVERLAP["enabled"] and device.type == "cuda"):
+        launch()
+        return
+    side = side_stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
     with torch.cuda.stream(side):
-        wgrad_accumulate(gw, dy, x)
-    _OVERLAP["keep"].append((dy, x))
+        launch()
+    _OVERLAP["keep"].append(keep)
     _OVERLAP["pending"].add(side.device.index)
+
+
+def wgrad_outstanding():  # for tests: copies of (devices with un-joined side-stream wgrads, the operands kept)
+    return set(_OVERLAP["pending"]), list(_OVERLAP["keep"])
 
 
 def wgrad_accumulate(gw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor):
@@ -129,17 +137,13 @@ def wgrad_accumulate(gw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor):
 
 
 # ---- which GEMM runs the PLAIN projection products (forward / input gradient, lm head)
-#   "blas" hipBLASLt through torch.mm -- the default: over the ten plain Llama-150M products the own
-#          ping-pong kernel reaches 0.942x of it (w128 0.918x), and the bf16 step with --proj-gemm pp is
-#          0.983x (round 6, profiles/r6_gemm_vb.md); every fused product and every weight gradient is on
-#          the own kernels
-#   "pp"   own ping-pong MFMA kernel (csrc/gemm_pp.hip; ops.gemm.gemm_pp) for every projection
-#   "short" own kernel for the short-K products (K <= 1024: o forward / dgrad, lm-head logits); hipBLASLt for
-#          the long-K dgrads (0.86-0.94x there)
-#   "w128" own one-wave-per-SIMD kernel (csrc/gemm_w128.hip: hipBLASLt's K-loop shape, 128 x 128 per wave)
-# The FUSED products always run on the own kernel (they exist only there): RoPE in the q|k|v
-# projection's epilogue, SwiGLU in the gate|up projection's, the SwiGLU backward in the down
-# projection's dgrad.  Under --fp8 every product (lm head included) runs on the own fp8 kernel.
+#   "blas"  hipBLASLt through torch.mm for every plain product (the default)
+#   "pp"    the own ping-pong MFMA kernel (csrc/gemm_pp.hip; ops.gemm.gemm_pp) wherever it takes the shape
+#   "short" the same for the short-K products (K <= 1024: o forward / dgrad, lm-head logits), hipBLASLt otherwise
+#   "w128"  the own one-wave-per-SIMD kernel (csrc/gemm_w128.hip: 128 x 128 per wave) wherever "pp" would run
+# Measured per product and per step in profiles/r6_gemm_vb.md.  The FUSED products (RoPE in the q|k|v epilogue,
+# SwiGLU in the gate|up one, its backward in the down dgrad's) and the weight gradients always run on the own
+# kernels; under --fp8 every product (lm head included) runs on the own fp8 kernel.
 _PROJ = {"gemm": "blas", "rope": True, "mlp": True}
 
 
@@ -185,13 +189,9 @@ def mm_nt(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None) -> torch.T
     return torch.mm(a, b.t(), out=out) if out is not None else torch.mm(a, b.t())
 
 
-def _wgrad(gw, dy, x):
-    if gw is None:
-        return
-    if _OVERLAP["enabled"] and gw.is_cuda:
-        _wgrad_on_side_stream(gw, dy, x)
-    else:
-        wgrad_accumulate(gw, dy, x)
+def wgrad_bf16(gw, dy, x) -> None:  # gw += dy^T x (nothing when ``gw`` is None) through issue_wgrad
+    if gw is not None:
+        issue_wgrad(gw.device, lambda: wgrad_accumulate(gw, dy, x), (dy, x))
 
 
 # Grouped weight gradients (round 5): the MLP's down and gate|up weight gradients as ONE own-kernel launch
@@ -219,19 +219,10 @@ def wgrad2_accumulate(gw0, dy0, x0, gw1, dy1, x1) -> None:
 
 def _wgrad2(gw0, dy0, x0, gw1, dy1, x1):
     if gw0 is None or gw1 is None:
-        _wgrad(gw0, dy0, x0)
-        _wgrad(gw1, dy1, x1)
+        wgrad_bf16(gw0, dy0, x0)
+        wgrad_bf16(gw1, dy1, x1)
         return
-    if _OVERLAP["enabled"] and gw0.is_cuda:
-        cur = torch.cuda.current_stream(gw0.device)
-        side = _side_stream(gw0.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            wgrad2_accumulate(gw0, dy0, x0, gw1, dy1, x1)
-        _OVERLAP["keep"].append((dy0, x0, dy1, x1))
-        _OVERLAP["pending"].add(side.device.index)
-    else:
-        wgrad2_accumulate(gw0, dy0, x0, gw1, dy1, x1)
+    issue_wgrad(gw0.device, lambda: wgrad2_accumulate(gw0, dy0, x0, gw1, dy1, x1), (dy0, x0, dy1, x1))
 
 
 class LinearFn(torch.autograd.Function):
@@ -259,14 +250,12 @@ class LinearFn(torch.autograd.Function):
                 dx = torch.mm(dy, w)
         else:
             dx = None
-        _wgrad(ctx.gw, dy, x)
+        wgrad_bf16(ctx.gw, dy, x)
         return dx, None, None, None
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, wt: torch.Tensor = None) -> torch.Tensor:
     return LinearFn.apply(x, w, gw, wt)
-
-
 
 
 # ---------------------------------------------------------------------------------------------
@@ -294,7 +283,7 @@ class LinearRopeFn(torch.autograd.Function):
         x, wt = ctx.saved_tensors
         dy = dy.contiguous()
         dx = mm_nt(dy, wt) if ctx.needs_input_grad[0] else None
-        _wgrad(ctx.gw, dy, x)
+        wgrad_bf16(ctx.gw, dy, x)
         return dx, None, None, None, None, None, None, None, None
 
 
@@ -311,9 +300,9 @@ def mlp_fused_supported(y: torch.Tensor, w_gu: torch.Tensor, wt_gu, w_down: torc
 class MLPFn(torch.autograd.Function):
     """The whole SwiGLU MLP on the own GEMM with both activation passes fused away:
 
-      forward   gu, act = [gate|up GEMM + SwiGLU epilogue](y)      (gu kept for the backward; by default in the
-                                                                  coefficient form [d act/d gate | d act/d up],
-                                                                  ops.gemm.set_mlp_coef)
+      forward   gu, act = [gate|up GEMM + SwiGLU epilogue](y)      (gu, for the matching dswiglu GEMM only, is
+                                                                  [gate | up], or by ops.gemm.mlp_coef() (default)
+                                                                  [A | B] = [d act/d gate | d act/d up])
                 m       = act . W_down^T
       backward  dgu     = [down dgrad GEMM + SwiGLU-backward epilogue](dm, W_down^T copy, gu)
                           -- d(act) is never stored
@@ -341,9 +330,9 @@ class MLPFn(torch.autograd.Function):
             dy = mm_nt(dgu, wt_gu) if ctx.needs_input_grad[0] else None
             _wgrad2(gw_down, dm, act, gw_gu, dgu, y)
             return dy, None, None, None, None, None, None
-        _wgrad(gw_down, dm, act)
+        wgrad_bf16(gw_down, dm, act)
         dy = mm_nt(dgu, wt_gu) if ctx.needs_input_grad[0] else None
-        _wgrad(gw_gu, dgu, y)
+        wgrad_bf16(gw_gu, dgu, y)
         return dy, None, None, None, None, None, None
 
 

@@ -159,8 +159,8 @@ def claim_compute_queues(dev: torch.device) -> None:
     other queues and the overlapped backward ran 2 % slower (bench.py, one-rank group vs none, with the
     side stream on: 330.6 vs 323.6 ms per step; serialized: equal -- round 5, gpurun_out r5d / r5g)."""
     torch.zeros(1, device=dev).add_(1)  # first use of the compute (null) stream
-    from ..ops.linear import _side_stream
-    side = _side_stream(dev)
+    from ..ops.linear import side_stream
+    side = side_stream(dev)
     with torch.cuda.stream(side):
         torch.zeros(1, device=dev).add_(1)
     torch.cuda.synchronize(dev)

@@ -266,7 +266,7 @@ def test_loss_stats_leaves_no_trace(case):
     m.train()
     torch.cuda.synchronize()
     _same(before, _snapshot(m))
-    assert getattr(m, "_lm_y8", None) is None
+    assert m.proj.lm_y8 is None
     s = a.tolist()
     assert s[1] == B * (T - 1) and 0 <= s[2] <= s[1] and s[0] / s[1] > 1.0
     # left-padded batch: the 9 pads carry label -100; position t predicts label t + 1, so labels 1..8 ignore 8

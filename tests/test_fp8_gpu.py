@@ -357,7 +357,7 @@ def test_fp8_lm_head_tracks_bf16_one_step():
     res = {}
     for use in (False, True):
         gw = torch.zeros(V, d, device="cuda")
-        f8 = (fp8.Fp8Linears("cuda", wgrad_fp8=True), 0, None) if use else None
+        f8 = fp8.Fp8Linears("cuda", wgrad_fp8=True) if use else None
         yy = y.detach().clone().requires_grad_(True)
         loss = lm_head_ce(yy, w, gw, t, 1.0, f8=f8)
         loss.backward()
@@ -391,7 +391,7 @@ def test_fp8_lm_head_fused_dlogits_match_separate_cast():
             for _ in range(2):
                 gw = torch.zeros(V, d, device="cuda")
                 yy = y.clone().requires_grad_(True)
-                loss = lm_head_ce(yy, w, gw, t, 1.0, f8=(lin, 0, None))
+                loss = lm_head_ce(yy, w, gw, t, 1.0, f8=lin, version=0, y8=None)
                 loss.backward()
                 join_wgrad()
             torch.cuda.synchronize()

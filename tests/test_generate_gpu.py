@@ -170,7 +170,7 @@ def test_fp8_model_generates_on_bf16_projections():
             assert torch.equal(_ints(before[k].reshape(-1)), _ints(after[k].reshape(-1))), k
         else:
             assert before[k] == after[k], k
-    assert getattr(m8, "_lm_y8", None) is None
+    assert m8.proj.lm_y8 is None
     b, lb = mb.generate(ids[:, :12], hip_graph=False, **kw)
     assert torch.equal(a, b) and torch.equal(la.view(torch.int32), lb.view(torch.int32))
     with pytest.raises(ValueError):

@@ -254,8 +254,8 @@ def test_dgrad_transposed_weights(graphed):
         else:
             m(ids, labels=ids, loss_scale=0.5).loss.backward()
         torch.cuda.synchronize()
-        assert len(m._wt_cache) == 4 * cfg.num_hidden_layers + 1
-        for key, (wt, ver, w) in m._wt_cache.items():
+        assert len(m.proj.wt_cache) == 4 * cfg.num_hidden_layers + 1
+        for key, (wt, ver, w) in m.proj.wt_cache.items():
             assert ver == m.store.version, key
             assert torch.equal(wt, w.t()), key
     finally:
