@@ -1,8 +1,8 @@
 """Text generation on the MI355X: bf16, the tiny model (nh = nkv = 4, hd 32) and a GQA model with rep 4 (hd 64), the
 HIP path of every op.
 
-The float64 reference of the logits is a plain Llama forward written here (float64, CPU) on the bf16-rounded weights
-the GPU model computes with -- never the code under test.  The cached decode step and the full forward of the same
+The float64 reference of the logits is the plain Llama forward of tests/_model_oracle.py (float64, CPU) on the
+bf16-rounded weights the GPU model computes with -- never the code under test.  The cached decode step and the full forward of the same
 prefix go through the same bf16 GEMMs and norms and differ in the attention kernel and in where RoPE rounds, so the
 cached logits must be as close to the reference as the full-forward logits are: per step,
 max|cached - ref| <= 2 max|full - ref|.  docs/PARITY.md (Generation) has the measured ratios.
@@ -17,9 +17,9 @@ import torch
 from nanodiloco_amd import ops
 from nanodiloco_amd.config import LlamaConfig, resolve_llama_config
 from nanodiloco_amd.models import LlamaForCausalLM
-from nanodiloco_amd.ops import reference as ref
 
 from ._frames import _ints
+from ._model_oracle import forward64
 from ._mp import ROOT, child_env
 
 pytestmark = pytest.mark.gpu
@@ -47,45 +47,6 @@ def _config(name):
     return LlamaConfig.from_dict(GQA)
 
 
-def forward64(m, ids, kstart=None):
-    """Llama forward in float64 on the CPU from the weights ``m`` computes with (bf16 shadow for the projections and
-    the lm head, fp32 master for the norms and the embedding); logits [B, T, V]."""
-    c = m.config
-    nh, nkv, hd, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-    W = lambda n: m.store.shadow_view(n).detach().double().cpu()
-    M = lambda n: m.store.master_view(n).detach().double().cpu()
-    ids = ids.cpu()
-    B, T = ids.shape
-    cos, sin = ref.rope_tables(T, hd, c.rope_theta, c.rope_scaling)
-    cos, sin = cos.double(), sin.double()
-
-    def norm(x, w):
-        return w * (x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps))
-
-    t = torch.arange(T)
-    ok = (t[None, :] <= t[:, None])[None].expand(B, T, T).clone()
-    if kstart is not None:
-        ok &= t.view(1, 1, T) >= kstart.cpu().long().view(B, 1, 1)
-    h = M("model.embed_tokens.weight")[ids]
-    for i in range(c.num_hidden_layers):
-        p = f"model.layers.{i}."
-        y = norm(h, M(p + "input_layernorm.weight"))
-        q = (y @ W(p + "self_attn.q_proj.weight").t()).view(B, T, nh, hd).transpose(1, 2)
-        k = (y @ W(p + "self_attn.k_proj.weight").t()).view(B, T, nkv, hd).transpose(1, 2)
-        v = (y @ W(p + "self_attn.v_proj.weight").t()).view(B, T, nkv, hd).transpose(1, 2)
-        q, k = ref.apply_rope(q, cos, sin), ref.apply_rope(k, cos, sin)
-        k, v = k.repeat_interleave(nh // nkv, dim=1), v.repeat_interleave(nh // nkv, dim=1)
-        s = (q @ k.transpose(-1, -2)) * hd ** -0.5
-        # a pad query row has no key: probabilities 0 (not NaN), as every attention path of the project gives
-        a = torch.softmax(s.masked_fill(~ok[:, None], float("-inf")), dim=-1).nan_to_num(0.0) @ v
-        h = h + a.transpose(1, 2).reshape(B, T, nh * hd) @ W(p + "self_attn.o_proj.weight").t()
-        y = norm(h, M(p + "post_attention_layernorm.weight"))
-        g, u = y @ W(p + "mlp.gate_proj.weight").t(), y @ W(p + "mlp.up_proj.weight").t()
-        h = h + (g * torch.sigmoid(g) * u) @ W(p + "mlp.down_proj.weight").t()
-    lm = "lm_head.weight" if not c.tie_word_embeddings else "model.embed_tokens.weight"
-    return norm(h, M("model.norm.weight")) @ W(lm).t()
-
-
 @pytest.mark.parametrize("name", ["tiny", "gqa"])
 def test_cached_logits_against_float64(name):
     cfg = _config(name)
@@ -97,7 +58,7 @@ def test_cached_logits_against_float64(name):
     mask[1, :5] = 0  # one left-padded row
     seq, cached = m.generate(ids, mask, max_new_tokens=n, eos_token_id=None, hip_graph=False, return_logits=True)
     full_mask = torch.cat([mask, torch.ones(B, n, dtype=torch.long, device=DEV)], dim=1)
-    ref64 = forward64(m, seq, ops.key_start(full_mask))
+    ref64 = forward64(m, seq.cpu(), ops.key_start(full_mask).cpu())  # float64 on the CPU, as before
     worst = 0.0
     for j in range(n):
         L = T + j
