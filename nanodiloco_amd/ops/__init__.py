@@ -17,6 +17,7 @@ from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov, fra
 from .muon import ns_gram, ns_poly, ns_update, ns_iterate, newton_schulz, muon_step, adamw_step_spans, \
     MuonPlan, AdamWSpans
 from .qcomm import pseudograd_q, qreduce, outer_nesterov_q, pseudograd_q_ef, qreduce_ef
+from .sparse_comm import pseudograd_topk, outer_nesterov_topk, topk_slot_bytes, densify
 from .determinism import set_deterministic, deterministic
 from . import reference
 
@@ -27,5 +28,6 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "KVCache", "attention_decode", "cache_fill", "decode_split",
            "lm_head_ce", "lm_head_loss",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
-           "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "frag_pseudograd", "frag_outer_mix", "SpanTable", "reference",
+           "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "pseudograd_topk", "outer_nesterov_topk",
+           "topk_slot_bytes", "densify","frag_pseudograd", "frag_outer_mix", "SpanTable", "reference",
            "ns_gram", "ns_poly", "ns_update", "ns_iterate", "newton_schulz", "muon_step", "adamw_step_spans", "MuonPlan", "AdamWSpans"]

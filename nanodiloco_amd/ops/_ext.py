@@ -187,8 +187,11 @@ def _declare(L: ctypes.CDLL):
         "nd_pseudograd_q_ef": [P, P, P, L64, P, L64, L64, I, P],
         "nd_qreduce_ef": [P, I, L64, I, P, P, P],
         "nd_outer_nesterov_q": [P, P, P, I, L64, P, P, I, L64, F, F, F, I, P],
+        # top-k sparse outer transport (csrc/sparse_comm.hip)
+        "nd_pseudograd_topk": [P, P, P, L64, P, I, I, P],
+        "nd_outer_nesterov_topk": [P, P, P, I, I, I, P, P, I, L64, F, F, F, I, P],
         # fp8 quantisation
-        "nd_fp8_cast": [P, I, L64, P, P, I, P, I, P],
+        "nd_fp8_cast":[P, I, L64, P, P, I, P, I, P],
         "nd_fp8_cast_t": [P, I, I, I, L64, P, P, P, I, P, I, P],
         # projection GEMMs (C = A B^T) and their fused epilogues
         # ping-pong projection GEMMs (csrc/gemm_pp.hip)

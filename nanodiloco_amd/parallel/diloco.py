@@ -15,7 +15,7 @@ pseudo-gradient.  Capability parity with ``class Diloco`` (REF/nanodiloco/diloco
   avg_sync_time always 0 (:62-64, dead)          real: wall time of every outer step (host) and
                                                  device time of its collectives (HIP events)
 
-Extensions (north star).  How the pseudo-gradient travels is one of three transports
+Extensions (north star).  How the pseudo-gradient travels is one of four transports
 (``parallel/transports.py``, whose classes document the protocols); :func:`_check_options` has every rule
 about which options go together:
 * ``comm_dtype`` fp32 / bf16 (half the bytes / outer step), ``overlap=True`` (the DELAYED outer update: one
@@ -25,6 +25,8 @@ about which options go together:
   :class:`~.transports.QuantisedTransport`;
 * ``fragments=P`` with ``fragment_pattern``, ``stream_overlap``, ``stream_alpha`` (Streaming DiLoCo), driven by
   :meth:`Diloco.stream_step`: :class:`~.transports.StreamingTransport`;
+* ``topk=K`` (--comm-topk; ``comm_dtype`` fp32 / bf16 is then the dtype of the values sent): the K largest entries
+  of every 4096-element chunk travel, the rest waits in an fp32 residual: :class:`~.transports.TopKTransport`;
 * ``inner_dp > 1`` (two-level): the W/K workers' outer all-reduce is sharded over the K GPUs of a
   worker (each reduces 1/K of the pseudo-gradient over its outer group, then the worker
   all-gathers the updated weights), so cross-worker bytes per GPU drop by K.
@@ -41,15 +43,18 @@ from ..utils.schedule import CosineWarmupSchedule
 from .comm import FlatCommunicator
 from .dist import DistEnv
 from .fragments import PATTERNS
-from .transports import DenseTransport, QuantisedTransport, StepTimer, StreamingTransport
+from ..ops.sparse_comm import CHUNK as TOPK_CHUNK
+from .transports import DenseTransport, QuantisedTransport, StepTimer, StreamingTransport, TopKTransport
 from .transports import quantised_bits  # also the name existing imports of it use
 
 
 def _check_options(flat_store: bool, comm_dtype=torch.float32, overlap=False, offload_snapshot=False, inner_dp=1,
                    error_feedback=False, fragments=0, fragment_pattern="strided", stream_overlap=0, stream_alpha=0.0,
-                   num_layers=0, inner_steps=0) -> int:
+                   num_layers=0, inner_steps=0, topk=0) -> int:
     """Every rule about which options go together, checked before a transport exists.  Returns the bits of
     the quantised transport (0: fp32 / bf16)."""
+    if topk:
+        _check_topk(flat_store, comm_dtype, overlap, error_feedback, fragments, topk)
     if not flat_store:
         if fragments:
             raise ValueError("Streaming DiLoCo (fragments > 0) needs the flat-store Llama of Diloco: "
@@ -86,6 +91,24 @@ def _check_options(flat_store: bool, comm_dtype=torch.float32, overlap=False, of
     return qbits
 
 
+def _check_topk(flat_store: bool, comm_dtype, overlap, error_feedback, fragments, topk) -> None:
+    """The rules of the top-k sparse transport (``topk`` > 0, --comm-topk)."""
+    if not flat_store:
+        raise ValueError("top-k sparse transport (topk > 0, --comm-topk) needs the flat-store Llama of Diloco: "
+                         "ModuleDiloco does not take it")
+    if not 1 <= int(topk) <= TOPK_CHUNK:
+        raise ValueError(f"topk (--comm-topk) must be in [1, {TOPK_CHUNK}] entries per chunk of {TOPK_CHUNK}, got {topk}")
+    if comm_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"top-k sparse transport (topk > 0, --comm-topk) sends fp32 or bf16 values, not comm_dtype "
+                         f"{comm_dtype}: int8 / int4 block quantisation is another transport")
+    for on, what in ((error_feedback, "error_feedback=True (--comm-error-feedback): top-k always carries its own "
+                                      "residual, and that flag belongs to the quantised transport"),
+                     (overlap, "overlap=True (--overlap-outer)"),
+                     (bool(fragments), "Streaming DiLoCo (fragments > 0, --streaming-fragments)")):
+        if on:
+            raise ValueError(f"top-k sparse transport (topk > 0, --comm-topk) is not supported together with {what}")
+
+
 class Diloco:
     """Flagship DiLoCo on the flat-store Llama.  Any other ``nn.Module`` (with plain torch optimizers)
     is dispatched to :class:`~nanodiloco_amd.parallel.module_diloco.ModuleDiloco`, which has the
@@ -94,7 +117,8 @@ class Diloco:
     def __new__(cls, model, *args, **kwargs):
         if not isinstance(model, LlamaForCausalLM):
             from .module_diloco import ModuleDiloco
-            _check_options(False, fragments=kwargs.get("fragments"), error_feedback=kwargs.pop("error_feedback", False))
+            _check_options(False, fragments=kwargs.get("fragments"), error_feedback=kwargs.pop("error_feedback", False),
+                           topk=kwargs.pop("topk", 0))
             return ModuleDiloco(model, *args, **kwargs)
         return super().__new__(cls)
 
@@ -104,7 +128,7 @@ class Diloco:
                  env: Optional[DistEnv] = None, comm_dtype: torch.dtype = torch.float32, bucket_mb: float = 128.0,
                  overlap: bool = False, offload_snapshot: bool = False, debug_checks: bool = False,
                  broadcast_init: bool = True, fragments: int = 0, fragment_pattern: str = "strided",
-                 stream_overlap: int = 0, stream_alpha: float = 0.0, error_feedback: bool = False):
+                 stream_overlap: int = 0, stream_alpha: float = 0.0, error_feedback: bool = False, topk: int = 0):
         self.model = model
         self.store = model.store
         self.inner_optimizer = inner_optimizer
@@ -122,9 +146,10 @@ class Diloco:
         self.fragment_pattern = fragment_pattern
         self.stream_overlap = int(stream_overlap)
         self.stream_alpha = float(stream_alpha)
+        self.topk = int(topk)
         qbits = _check_options(True, comm_dtype, overlap, offload_snapshot, self.env.inner_dp, error_feedback,
                                self.fragments, fragment_pattern, self.stream_overlap, self.stream_alpha,
-                               model.config.num_hidden_layers, inner_steps)
+                               model.config.num_hidden_layers, inner_steps, self.topk)
         e = self.env
         f = e.force_collectives
         kw = dict(impl=e.comm_impl, device=e.device, timeout_s=e.timeout_s)
@@ -153,7 +178,9 @@ class Diloco:
         self.local_step = 0
         self.outer_step_count = 0
         # ---- the one place that tells the transports apart
-        if qbits:
+        if self.topk:
+            self.transport = TopKTransport(self, self.topk, comm_dtype)
+        elif qbits:
             self.transport = QuantisedTransport(self, qbits, self.error_feedback)
         elif fragments:
             self.transport = StreamingTransport(self, comm_dtype, self.fragments, fragment_pattern,
@@ -200,7 +227,7 @@ class Diloco:
         return self.scheduler.lr()
 
     _TRANSPORT_NAMES = ("delta", "qbits", "qef_send", "qef_reduce", "error_feedback_state", "frag_tables", "frag_steps",
-                        "fragment_sync_count")
+                        "fragment_sync_count", "topk_residual")
 
     def __getattr__(self, name):
         """Read-only forwards of the active transport's public state (absent where that transport has none)."""

@@ -1,4 +1,4 @@
-"""The three ways :class:`~nanodiloco_amd.parallel.diloco.Diloco` moves its pseudo-gradient.  Each transport owns
+"""The four ways :class:`~nanodiloco_amd.parallel.diloco.Diloco` moves its pseudo-gradient.  Each transport owns
 its wire buffers, its protocol and the part of a checkpoint that only it understands; ``Diloco`` builds exactly
 one (``Diloco.transport``) and keeps what does not depend on it: the snapshot, the counters, the communicators,
 ``_after_update`` and the :class:`StepTimer`.
@@ -7,7 +7,7 @@ What ``Diloco`` and ``utils/checkpoint.py`` ask of a transport: ``bytes_per_step
 ``finalize()``, ``local_weights_differ``, and for checkpoints ``rank_state() -> (tensors, scalars)`` (this rank's
 files), ``shared_state() -> (trainer_state.json entries, config.json flags)`` and ``load_state(per, scal, shared)
 -> lines to log`` (``per`` / ``scal``: this rank's OWN files, empty for a worker the checkpoint did not have).
-Dense and quantised run ``step(phases)``; streaming runs ``stream_step(t)`` and ``flush()``.
+Dense, quantised and top-k run ``step(phases)``; streaming runs ``stream_step(t)`` and ``flush()``.
 """
 from __future__ import annotations
 
@@ -17,11 +17,12 @@ from typing import Optional
 import torch
 
 from .. import ops
-from ..ops import qcomm
+from ..ops import qcomm, sparse_comm
 from .comm import PendingAllReduce, plan_buckets
 from .fragments import fragment_due, plan_fragments
 
 _EF_IGNORED = "checkpoint holds error-feedback residuals; this run has no --comm-error-feedback: ignored"
+_TOPK_IGNORED = "checkpoint holds a top-k residual (topk.residual); this run has no --comm-topk: ignored"
 
 
 def quantised_bits(comm_dtype) -> int:
@@ -107,9 +108,10 @@ class Transport:
     def load_state(self, per, scal, shared) -> list:
         if shared.get("pending_outer"):
             raise RuntimeError("checkpoint holds a pending overlapped outer step: resume with --overlap-outer")
-        if ("qef.send" in per or "qef.reduce" in per) and (self.d is None or self.d.env.rank == 0):
-            return [_EF_IGNORED]
-        return []
+        if self.d is not None and self.d.env.rank != 0:
+            return []
+        return ([_EF_IGNORED] if "qef.send" in per or "qef.reduce" in per else []) + \
+            ([_TOPK_IGNORED] if "topk.residual" in per else [])
 
 
 class DenseTransport(Transport):
@@ -376,14 +378,128 @@ class QuantisedTransport(Transport):
         return {"pending_outer": False, **feedback}, {}
 
     def load_state(self, per, scal, shared) -> list:
-        super().load_state({}, scal, shared)  # refuses a pending overlapped step
+        # refuses a pending overlapped step; a top-k residual is not this transport's
+        other = super().load_state({k: v for k, v in per.items() if k.startswith("topk.")}, scal, shared)
         send, reduce, saved = per.get("qef.send"), per.get("qef.reduce"), shared.get("comm_error_feedback")
         had = saved is not None or send is not None
         if not (had or self.error_feedback):
-            return []
+            return other
         lines = self.load_error_feedback_state(send, reduce, saved)
         # every rank that lost residuals the checkpoint had says so; the rest is rank 0's to log
-        return lines if self.d.env.rank == 0 or (self.error_feedback and had and send is None) else []
+        return other + (lines if self.d.env.rank == 0 or (self.error_feedback and had and send is None) else [])
+
+
+class _TopKBucket:
+    """One bucket of the top-k outer step: elements [x, y) of the owned span (whole chunks, except at the span's
+    end), W slots of ``slot`` bytes back to back in ``gath``."""
+
+    __slots__ = ("x", "y", "slot", "gath")
+
+    def __init__(self, x, y, slot, gath):
+        self.x, self.y, self.slot, self.gath = x, y, slot, gath
+
+
+class TopKTransport(Transport):
+    """Top-k sparse transport with error feedback (``ops/sparse_comm.py``, docs/DESIGN.md §4): of every chunk of 4096
+    elements of the span this GPU owns, only the ``k`` entries of ``(sync - master) + e`` with the largest magnitude
+    travel, as ``uint16`` indices with fp32 or bf16 values; ``e`` (fp32, one element per owned element, zero at the
+    start) keeps what did not.  Indices differ per worker, so nothing can be reduced on the way: the step is
+    ``nd_pseudograd_topk`` -> all-gather of the W slots -> ``nd_outer_nesterov_topk`` per bucket, and EVERY worker,
+    the sender included, updates from the gathered bytes in worker order, so theta_sync and the master stay
+    bit-identical across workers.  The residual is this rank's checkpoint state (``topk.residual``)."""
+
+    def __init__(self, diloco, k: int, value_dtype):
+        super().__init__(diloco)
+        self.k, self.value_dtype = int(k), value_dtype
+        a, b = diloco.my_shard
+        self.residual = torch.zeros(b - a, dtype=torch.float32, device=diloco.store.device)
+        self._plan = self._plan_buckets(b - a)
+
+    @property
+    def topk_residual(self) -> torch.Tensor:
+        return self.residual
+
+    @property
+    def bytes_per_step(self) -> int:
+        """this worker's slots (what it contributes to the all-gathers), padding included"""
+        return sum(bk.slot for bk in self._plan)
+
+    @property
+    def buckets_per_step(self) -> int:
+        return len(self._plan)
+
+    def _plan_buckets(self, length: int) -> list:
+        """Runs of whole chunks whose W slots fit ``bucket_bytes`` (at least one chunk), each with one persistent
+        uint8 ``gath`` buffer of W slots."""
+        d = self.d
+        w = max(1, d.env.num_workers)
+        vs = 4 if self.value_dtype == torch.float32 else 2
+        # 32: the two paddings of a slot
+        chunks = max(1, (d.outer_comm.bucket_bytes // w - 32) // (self.k * (2 + vs)))
+        dev = d.store.device
+        plan = []
+        for x, y in plan_buckets(0, length, 1, chunks * sparse_comm.CHUNK, align=sparse_comm.CHUNK):
+            slot = sparse_comm.topk_slot_bytes(y - x, self.k, self.value_dtype)
+            plan.append(_TopKBucket(x, y, slot, torch.zeros(w * slot, dtype=torch.uint8, device=dev)))
+        return plan
+
+    def step(self, phases: bool):
+        """Every bucket's select + all-gather is issued first, then each bucket is updated while the later ones
+        are still being gathered; the host never blocks (GPU)."""
+        d, timer = self.d, self.d.timer
+        ev0, t0 = timer.start(phases)
+        sync = d._sync_on_device()
+        e, opt = d.env, d.outer_optimizer
+        w, r = max(1, e.num_workers), e.worker
+        a, _ = d.my_shard
+        master, mom = d.store.master, opt.momentum_buffer
+        sh_full = d.store.separate_shadow
+        first = opt.step_count == 0
+        comm = d.outer_comm
+        gathered = []
+        for bk in self._plan:
+            ga, gb = a + bk.x, a + bk.y
+            ops.pseudograd_topk(sync[ga:gb], master[ga:gb], self.residual[bk.x:bk.y],
+                                bk.gath[r * bk.slot:(r + 1) * bk.slot], self.k, self.value_dtype)
+            gathered.append(comm.all_gather_async(bk.gath, r))
+        timer.phase()
+        if timer.phased:
+            for work in gathered:
+                work.wait()  # serialized: the compute stream waits for every bucket here
+            timer.phase()
+        d.outer_step_count += 1
+        for bk, work in zip(self._plan, gathered):
+            work.wait()
+            ga, gb = a + bk.x, a + bk.y
+            ops.outer_nesterov_topk(master[ga:gb], sync[ga:gb], bk.gath, w, self.k, self.value_dtype, mom[ga:gb],
+                                    sh_full[ga:gb] if sh_full is not None else None, 1.0 / w, opt.lr, opt.momentum,
+                                    first)
+        d._after_update(sync, sh_full, ev0, t0)
+
+    def rank_state(self):
+        return {"topk.residual": self.residual}, {}
+
+    def shared_state(self):
+        name = "fp32" if self.value_dtype == torch.float32 else "bf16"
+        return {"pending_outer": False,
+                "comm_topk": {"k": self.k, "chunk": sparse_comm.CHUNK, "value_dtype": name}}, {}
+
+    def load_state(self, per, scal, shared) -> list:
+        """The residual is an fp32 amount still owed, indexed by element of the owned span: restored whenever its
+        length matches -- k, the value dtype and the number of workers may differ --, else zero.  A rank without
+        one (a checkpoint of another transport, a worker the checkpoint did not have) starts at zero."""
+        lines = super().load_state({k: v for k, v in per.items() if k.startswith("qef.")}, scal, shared)
+        saved = per.get("topk.residual")
+        self.residual.zero_()
+        if saved is None:
+            if shared.get("comm_topk") is not None:  # the checkpoint had residuals, this rank has none in it
+                lines.append("no top-k residual in the checkpoint for this rank: starting from zero")
+        elif saved.numel() == self.residual.numel():
+            self.residual.copy_(saved)
+        else:
+            lines.append(f"topk.residual has {saved.numel()} elements, this rank owns {self.residual.numel()}: "
+                         f"starting from zero")
+        return lines
 
 
 class StreamingTransport(Transport):

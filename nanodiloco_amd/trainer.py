@@ -68,6 +68,9 @@ class TrainArgs:
     comm_dtype: str = "fp32"       # fp32 | bf16 | int8 | int4 (block-quantised outer transport, parallel/diloco.py)
     comm_error_feedback: bool = False  # with int8 | int4: carry what quantisation did not deliver into the next
                                        # outer step (two fp32 residuals per GPU, docs/DESIGN.md "Error feedback")
+    comm_topk: int = 0             # K > 0: top-k sparse outer transport -- of every 4096-element chunk only the K
+                                   # largest entries travel (values in --comm-dtype fp32 | bf16), the rest waits in
+                                   # an fp32 residual (docs/DESIGN.md "Top-k sparse transport"); 0 = off
     bucket_mb: float = 128.0
     overlap_outer: bool = False
     offload_snapshot: bool = False
@@ -204,6 +207,16 @@ class Trainer:
         self.args = a = args
         if a.total_steps % a.inner_steps:
             raise ValueError("total_steps must be a multiple of inner_steps")  # REF main.py:69
+        if a.comm_topk:
+            if not 1 <= a.comm_topk <= 4096:
+                raise ValueError(f"--comm-topk must be in [1, 4096] entries per chunk of 4096 (0 = off), got {a.comm_topk}")
+            for on, what in ((a.comm_dtype in ("int8", "int4"), f"--comm-dtype {a.comm_dtype}: top-k values travel "
+                                                                f"as --comm-dtype fp32 | bf16"),
+                             (a.comm_error_feedback, "--comm-error-feedback: top-k always carries its own residual"),
+                             (a.overlap_outer, "--overlap-outer"),
+                             (a.streaming_fragments > 0, "--streaming-fragments")):
+                if on:
+                    raise ValueError(f"--comm-topk is not supported together with {what}")
         if a.comm_error_feedback and a.comm_dtype not in ("int8", "int4"):
             raise ValueError(f"--comm-error-feedback needs the quantised transport (--comm-dtype int8 | int4), not "
                              f"--comm-dtype {a.comm_dtype}: fp32 / bf16 pseudo-gradients are all-reduced as they are")
@@ -256,7 +269,8 @@ class Trainer:
                              overlap=a.overlap_outer, offload_snapshot=a.offload_snapshot,
                              debug_checks=a.debug_checks, fragments=a.streaming_fragments,
                              fragment_pattern=a.streaming_pattern, stream_overlap=a.streaming_overlap_steps,
-                             stream_alpha=a.streaming_alpha, error_feedback=a.comm_error_feedback)
+                             stream_alpha=a.streaming_alpha, error_feedback=a.comm_error_feedback,
+                             topk=a.comm_topk)
         if a.streaming_fragments and a.elastic_resume:
             raise ValueError("--elastic-resume is not supported with --streaming-fragments: a streaming checkpoint "
                              "holds per-worker local weights")

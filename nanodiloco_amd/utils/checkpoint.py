@@ -41,6 +41,12 @@ checkpoint resumes with the flag on from zero residuals, a checkpoint with resid
 them, ``qef.send`` survives int8 <-> int4 and ``--elastic-resume`` (surviving ranks; new workers start at zero),
 ``qef.reduce`` only an unchanged plan and worker count.
 
+With ``--comm-topk K`` (top-k sparse transport) every rank file carries ``topk.residual`` (fp32, one element per
+element of the span the rank owns) and ``trainer_state.json`` records ``comm_topk: {k, chunk, value_dtype}``.  The
+residual is an amount still owed, whatever it was selected with: it is restored whenever its length matches (another K,
+another value dtype, another number of workers), else the rank starts from zero with a logged line; a rank without one
+starts at zero, and a run without ``--comm-topk`` ignores it with a logged line (``TopKTransport.load_state``).
+
 Crash consistency (round 5): every rank writes into ``<dir>.tmp``; after a barrier rank 0 adds
 ``COMPLETE.json`` and swaps the staging directory in (``<dir>`` -> ``<dir>.old``, ``<dir>.tmp`` -> ``<dir>``,
 then ``<dir>.old`` is removed), so a crash at any point of a save leaves the previous complete checkpoint
