@@ -9,11 +9,34 @@
 //   x <- (exp(x - lse) - [j == target]) * scale               (dlogits, compute dtype)
 // scale = loss_scale / n_valid lives in device memory (no host sync).  Rows whose target is
 // ignore_index contribute 0 loss and 0 gradient.  Larger vocabularies use the two-pass variant.
+//
+// z-loss (Z = true instantiations, nd_ce_z_fwd_bwd / nd_ce_z_fwd_bwd_q8): the objective gains z_coef * sum lse^2
+// over the valid rows, so with g = 1 + 2 z_coef lse (one scalar per row)
+//   x <- (exp(x - lse) * g - [j == target]) * scale
+// and lse^2 goes to an accumulator of its own (z_sum, or one store per row into row_z): the cross-entropy sum
+// never contains the z term.  Z = the kernel was instantiated with a ZArgs parameter; without one every
+// `if constexpr (Z)` is compiled out and the kernel is what it was.
 #include "common.h"
 #include <cstdio>
 #include <cstdlib>
 
 using namespace nd;
+
+// what the z instantiations take on top of the plain kernels' arguments
+struct ZArgs {
+  float coef;     // z_coef
+  float* z_sum;   // += sum lse^2 over the valid rows (one atomicAdd per row), unless row_z is given
+  float* row_z;   // per row: lse^2 (0 where the target is ignored); deterministic mode, no float atomic
+};
+// The kernels take it as a trailing parameter pack: empty (the plain kernels, whose signature and code stay as they
+// were) or one ZArgs (Z = true).
+__device__ __forceinline__ const ZArgs& zarg(const ZArgs& z) { return z; }
+
+// the row's z term, by thread 0 after the cross-entropy has gone out
+__device__ __forceinline__ void z_commit(const ZArgs& z, int64_t row, bool valid, float lse) {
+  if (z.row_z) z.row_z[row] = valid ? lse * lse : 0.f;
+  else if (valid) atomicAdd(z.z_sum, lse * lse);
+}
 
 template <int NT>
 __device__ __forceinline__ float block_max(float v, float* red) {
@@ -28,11 +51,12 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return t;
 }
 
-template <int DT, int CH>
+template <int DT, int CH, class... ZA>
 __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, const int64_t* __restrict__ targets,
                                                      float* __restrict__ loss_sum, const float* __restrict__ scale_p,
                                                      int V, int ignore, float* __restrict__ lse_out,
-                                                     float* __restrict__ row_loss) {
+                                                     float* __restrict__ row_loss, ZA... z) {
+  constexpr bool Z = sizeof...(ZA) > 0;
   __shared__ float red[8];
   const int64_t row = blockIdx.x;
   const int64_t base = row * (int64_t)V;
@@ -63,6 +87,8 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
   s = block_sum<256>(s, red);
   const float lse = m + __logf(s);
   const float sc = valid ? scale_p[0] : 0.f;
+  float scg = sc;  // Z: scale * g, the multiplier of the probabilities; the target column still subtracts scale
+  if constexpr (Z) scg = valid ? sc * fmaf(2.f * zarg(z...).coef, lse, 1.f) : 0.f;
   float picked = 0.f;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
@@ -73,7 +99,8 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
       for (int j = 0; j < 8; ++j) {
         const bool hit = (int64_t)(col + j) == tgt;
         if (hit) picked = x[c][j];
-        o[j] = (__expf(x[c][j] - lse) - (hit ? 1.f : 0.f)) * sc;
+        if constexpr (Z) o[j] = fmaf(__expf(x[c][j] - lse), scg, hit ? -sc : 0.f);
+        else o[j] = (__expf(x[c][j] - lse) - (hit ? 1.f : 0.f)) * sc;
       }
       Vec8<DT>::store(logits, base + col, o);
     }
@@ -86,6 +113,7 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
   if (threadIdx.x == 0) {
     if (row_loss) row_loss[row] = valid ? lse - picked : 0.f;  // deterministic mode: summed in order later
     else if (valid) atomicAdd(loss_sum, lse - picked);
+    if constexpr (Z) z_commit(zarg(z...), row, valid, lse);
   }
 }
 
@@ -97,11 +125,13 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
 // QF >= 0 (fp8 lm head, round 5): the dlogits go out ONLY as fp8 (QF: 0 e4m3, 1 e5m2) into q8.q [rows, V], from
 // the bf16-rounded values -- bitwise nd_fp8_cast over the bf16 dlogits, whose 4.2 GB write and re-read per
 // 65,536-row chunk this removes; amax partials as the other fused producers (common.h Fp8Out).
-template <int CH, int QF = -1>
+// Z: g folds into the multiplier that scales exp2(...) anyway, so the element loop is the same instructions.
+template <int CH, int QF = -1, class... ZA>
 __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logits, const int64_t* __restrict__ targets,
                                                       float* __restrict__ loss_sum, const float* __restrict__ scale_p,
                                                       int V, int ignore, float* __restrict__ lse_out,
-                                                     float* __restrict__ row_loss, Fp8Out q8) {
+                                                     float* __restrict__ row_loss, Fp8Out q8, ZA... z) {
+  constexpr bool Z = sizeof...(ZA) > 0;
   constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
   __shared__ float red[8];
   const int64_t row = blockIdx.x;
@@ -142,6 +172,8 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
 #pragma unroll
   for (int c = 0; c < CH; ++c) asm volatile("" : "+v"(x[c].x), "+v"(x[c].y), "+v"(x[c].z), "+v"(x[c].w));
   const float sc = valid ? scale_p[0] : 0.f;
+  float scg = sc;  // Z: scale * g, g = 1 + 2 z_coef lse
+  if constexpr (Z) scg = valid ? sc * fmaf(2.f * zarg(z...).coef, lse2 * LN2, 1.f) : 0.f;
   const float qsc = QF >= 0 ? q8.scale[0] : 1.f;
   float qmax = 0.f;
   float picked = 0.f;
@@ -153,8 +185,8 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
       float o[8];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        o[2 * j] = __builtin_amdgcn_exp2f(fmaf(lo_bf(u[j]), L2E, -lse2)) * sc;
-        o[2 * j + 1] = __builtin_amdgcn_exp2f(fmaf(hi_bf(u[j]), L2E, -lse2)) * sc;
+        o[2 * j] = __builtin_amdgcn_exp2f(fmaf(lo_bf(u[j]), L2E, -lse2)) * scg;
+        o[2 * j + 1] = __builtin_amdgcn_exp2f(fmaf(hi_bf(u[j]), L2E, -lse2)) * scg;
       }
       const unsigned d = (unsigned)(tgt - col);
       if (d < 8u) {  // this thread owns the target column
@@ -188,15 +220,17 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
   if (threadIdx.x == 0) {
     if (row_loss) row_loss[row] = valid ? lse - picked : 0.f;  // deterministic mode: summed in order later
     else if (valid) atomicAdd(loss_sum, lse - picked);
+    if constexpr (Z) z_commit(zarg(z...), row, valid, lse);
   }
 }
 
 // Generic two-pass variant (any V, scalar accesses): online max/sum, then gradient write.
-template <int DT>
+template <int DT, class... ZA>
 __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logits, const int64_t* __restrict__ targets,
                                                          float* __restrict__ loss_sum, const float* __restrict__ scale_p,
                                                          int V, int ignore, float* __restrict__ lse_out,
-                                                     float* __restrict__ row_loss) {
+                                                     float* __restrict__ row_loss, ZA... z) {
+  constexpr bool Z = sizeof...(ZA) > 0;
   __shared__ float red[8];
   const int64_t row = blockIdx.x;
   const int64_t base = row * (int64_t)V;
@@ -219,12 +253,16 @@ __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logi
   s = block_sum<256>(s, red);
   const float lse = gm + __logf(s);
   const float sc = valid ? scale_p[0] : 0.f;
+  float scg = sc;  // Z: scale * g, as in ce_reg_kernel
+  if constexpr (Z) scg = valid ? sc * fmaf(2.f * zarg(z...).coef, lse, 1.f) : 0.f;
   float picked = 0.f;
   for (int j = threadIdx.x; j < V; j += 256) {
     const float v = ld(j);
     const bool hit = (int64_t)j == tgt;
     if (hit) picked = v;
-    const float o = (__expf(v - lse) - (hit ? 1.f : 0.f)) * sc;
+    float o;
+    if constexpr (Z) o = fmaf(__expf(v - lse), scg, hit ? -sc : 0.f);
+    else o = (__expf(v - lse) - (hit ? 1.f : 0.f)) * sc;
     if (DT == BF16) reinterpret_cast<bf16_t*>(logits)[base + j] = f2bf(o);
     else reinterpret_cast<float*>(logits)[base + j] = o;
   }
@@ -234,6 +272,7 @@ __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logi
   if (threadIdx.x == 0) {
     if (row_loss) row_loss[row] = valid ? lse - picked : 0.f;  // deterministic mode: summed in order later
     else if (valid) atomicAdd(loss_sum, lse - picked);
+    if constexpr (Z) z_commit(zarg(z...), row, valid, lse);
   }
 }
 
@@ -290,5 +329,58 @@ ND_API int nd_ce_fwd_bwd_q8(void* logits, int dt, const int64_t* targets, float*
   else
     hipLaunchKernelGGL((ce_bf16_kernel<16, 1>), g, b, 0, s, (bf16_t*)logits, targets, loss_sum, scale, V, ignore, lse_out,
                        row_loss, q8);
+  ND_LAUNCH_CHECK();
+}
+
+// z-loss forms of the two entry points above: the same dispatch borders and, for _q8, the same acceptance rule.
+// loss_sum still receives the cross-entropy alone; sum lse^2 over the valid rows goes to z_sum (atomic), or with
+// row_z != nullptr as one store per row (deterministic mode; row_loss and row_z are chosen independently).
+static bool z_args_ok(const float* z_sum, const float* row_z, float z_coef) {
+  return (z_sum || row_z) && z_coef >= 0.f && z_coef <= 3.0e38f;  // refuses NaN and inf too
+}
+
+ND_API int nd_ce_z_fwd_bwd(void* logits, int dt, const int64_t* targets, float* loss_sum, float* z_sum,
+                           const float* scale, int64_t n, int V, int ignore, float* lse_out, float* row_loss,
+                           float* row_z, float z_coef, hipStream_t s) {
+  if (!z_args_ok(z_sum, row_z, z_coef)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  const ZArgs z{z_coef, z_sum, row_z};
+  dim3 g((unsigned)n), b(256);
+  if (V % 8 == 0 && V <= 256 * 8 * 16) {
+    if (V <= 256 * 8 * 4) {
+      if (dt == BF16) hipLaunchKernelGGL((ce_reg_kernel<BF16, 4, ZArgs>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, z);
+      else hipLaunchKernelGGL((ce_reg_kernel<F32, 4, ZArgs>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, z);
+    } else {
+      if (dt == BF16 && !g_ce_reg)
+        hipLaunchKernelGGL((ce_bf16_kernel<16, -1, ZArgs>), g, b, 0, s, (bf16_t*)logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss,
+                           Fp8Out{nullptr, nullptr, nullptr, 1, 0}, z);
+      else if (dt == BF16) hipLaunchKernelGGL((ce_reg_kernel<BF16, 16, ZArgs>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, z);
+      else hipLaunchKernelGGL((ce_reg_kernel<F32, 16, ZArgs>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, z);
+    }
+  } else {
+    if (dt == BF16) hipLaunchKernelGGL((ce_generic_kernel<BF16, ZArgs>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, z);
+    else hipLaunchKernelGGL((ce_generic_kernel<F32, ZArgs>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, z);
+  }
+  ND_LAUNCH_CHECK();
+}
+
+ND_API int nd_ce_z_fwd_bwd_q8(void* logits, int dt, const int64_t* targets, float* loss_sum, float* z_sum,
+                              const float* scale, int64_t n, int V, int ignore, float* lse_out, float* row_loss,
+                              float* row_z, float z_coef, void* q, const float* qscale, float* amax, int parts, int fmt,
+                              hipStream_t s) {
+  if (!z_args_ok(z_sum, row_z, z_coef)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (dt != BF16 || V % 8 != 0 || V <= 256 * 8 * 4 || V > 256 * 8 * 16 || g_ce_reg || !q || !qscale || !amax ||
+      parts < 1 || (fmt != 0 && fmt != 1))
+    return (int)hipErrorInvalidValue;
+  const Fp8Out q8{(uint8_t*)q, qscale, amax, parts, fmt};
+  const ZArgs z{z_coef, z_sum, row_z};
+  dim3 g((unsigned)n), b(256);
+  if (fmt == 0)
+    hipLaunchKernelGGL((ce_bf16_kernel<16, 0, ZArgs>), g, b, 0, s, (bf16_t*)logits, targets, loss_sum, scale, V, ignore, lse_out,
+                       row_loss, q8, z);
+  else
+    hipLaunchKernelGGL((ce_bf16_kernel<16, 1, ZArgs>), g, b, 0, s, (bf16_t*)logits, targets, loss_sum, scale, V, ignore, lse_out,
+                       row_loss, q8, z);
   ND_LAUNCH_CHECK();
 }

@@ -39,8 +39,10 @@ _CONFIG = object()  # generate(): "take it from the model config"
 
 @dataclasses.dataclass
 class CausalLMOutput:
-    loss: Optional[torch.Tensor] = None
+    loss: Optional[torch.Tensor] = None  # the objective: cross-entropy, plus the z term when model.z_loss > 0
     logits: Optional[torch.Tensor] = None
+    ce_loss: Optional[torch.Tensor] = None  # the cross-entropy part, detached (z_loss 0: ``loss``, detached)
+    z_loss: Optional[torch.Tensor] = None   # the weighted z term, detached; None when model.z_loss is 0
 
 
 class _GradHook(torch.autograd.Function):
@@ -72,6 +74,9 @@ class LlamaForCausalLM:
         # packed windows: attention stays inside each EOS-separated document (ops.doc_bounds)
         self.doc_mask = bool(doc_mask)
         self.debug_checks = False  # validate the derived bounds every forward (host sync: never under graph capture)
+        # z-loss coefficient of the training objective (--z-loss; ops/cross_entropy.py): 0.0 = off.  A hyperparameter,
+        # not state; evaluation (loss_stats) ignores it
+        self.z_loss = 0.0
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype
         # residual stream: fp32 (default, the autocast recipe) or bf16 (Megatron's default; ops/norm.py)
@@ -232,7 +237,7 @@ class LlamaForCausalLM:
         if labels is not None or targets is not None:
             if targets is None:
                 targets = ops.reference.shift_labels(labels, ops.IGNORE_INDEX)
-            out.loss = self.proj.lm_head_ce(y, targets.reshape(-1), loss_scale)
+            out.loss, out.ce_loss, out.z_loss = self.proj.lm_head_ce(y, targets.reshape(-1), loss_scale, self.z_loss)
         if return_logits or (labels is None and targets is None):
             with torch.no_grad():
                 B, T = input_ids.shape

@@ -164,6 +164,9 @@ def _declare(L: ctypes.CDLL):
         # loss
         "nd_ce_fwd_bwd": [P, I, P, P, P, L64, I, I, P, P, F, P],
         "nd_ce_fwd_bwd_q8": [P, I, P, P, P, L64, I, I, P, P, P, P, P, I, I, P],
+        # the same with z-loss: (+ z_sum after loss_sum, row_z and z_coef after row_loss)
+        "nd_ce_z_fwd_bwd": [P, I, P, P, P, P, L64, I, I, P, P, P, F, P],
+        "nd_ce_z_fwd_bwd_q8": [P, I, P, P, P, P, L64, I, I, P, P, P, F, P, P, P, I, I, P],
         # loss only (evaluation, csrc/ce_loss.hip): const logits, per-row loss / lse / top-1 hit
         "nd_ce_loss": [P, I, P, L64, I, I, P, P, P, P],
         # embedding

@@ -15,20 +15,33 @@ chunks; for each chunk:
 so only one chunk of logits ever exists and nothing [N, V]-sized survives the forward.
 ``s = loss_scale / n_valid`` is read from device memory (no host sync).
 
+z-loss (``z_loss`` = z_coef > 0, --z-loss; docs/DESIGN.md "z-loss"): the objective gains
+``z_coef * mean(lse^2)`` over the valid rows, lse = logsumexp(logits).  Nothing [N, V]-sized exists for an
+autograd-side term to attach to, so the term lives in the CE kernels: ``nd_ce_z_fwd_bwd`` /
+``nd_ce_z_fwd_bwd_q8`` are step 2 with ``dlogits = s * (softmax * (1 + 2 z_coef lse) - onehot)`` -- one more
+scalar per row -- and accumulate ``sum lse^2`` apart from the cross-entropy sum.  The returned loss is then
+the objective, cross-entropy + weighted z term; ``lm_head_ce_parts`` also gives the two parts as detached
+device scalars (no host sync).  With ``z_loss == 0.0`` the entry points called, the launches and every bit are
+those of the z-free path.
+
 fp8 (``f8`` = the model's ``Fp8Linears``, BASELINE config 5): the three GEMMs run on the own fp8 kernels --
 logits = e4m3 y8 . W8^T, the CE kernel writes the dlogits straight as e5m2 (delayed scaling, slot "x.lm";
 ``nd_ce_fwd_bwd_q8``, bitwise the bf16 dlogits + separate cast that the first step, which has no scale yet,
-still takes), dy = dlogits8 . (W^T)8^T and gW += dlogits8^T y8 (wgrad8_pp_kernel).  The returned loss is the
-unscaled mean over valid tokens (ignore_index=-100), matching ``HF/loss/loss_utils.py:32-71``.
+still takes; with z-loss the same pair is ``nd_ce_z_fwd_bwd_q8`` / ``nd_ce_z_fwd_bwd``), dy = dlogits8 . (W^T)8^T and
+gW += dlogits8^T y8 (wgrad8_pp_kernel).  The returned loss is the unscaled mean over valid tokens
+(ignore_index=-100), matching ``HF/loss/loss_utils.py:32-71``.
 
 Contract: the weight gradient is produced in the forward, assuming the loss is back-propagated
 with unit upstream gradient (``loss.backward()``); ``loss_scale`` is how callers scale it
-(e.g. 1/grad_accum).  The activation gradient is additionally multiplied by the upstream
-gradient, so ``dy`` is correct for any upstream value.
+(e.g. 1/grad_accum).  It scales the gradient of the whole objective -- with z-loss
+``loss_scale * (sum CE + z_coef * sum lse^2) / n_valid`` -- and never the returned loss or its parts.
+The activation gradient is additionally multiplied by the upstream gradient, so ``dy`` is correct for
+any upstream value.
 """
 from __future__ import annotations
 
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -58,9 +71,21 @@ def _chunks(n: int, V: int, elem: int, chunk_rows: int):
     return [(s, min(n, s + chunk)) for s in range(0, n, chunk)]
 
 
+class LMHeadLoss(NamedTuple):
+    """``loss``: the objective (differentiable); ``ce_loss``: its cross-entropy part; ``z_loss``: the weighted z
+    term ``z_coef * mean(lse^2)`` -- both detached device scalars, ``z_loss`` None when z-loss is off (then
+    ``ce_loss`` is ``loss``, detached)."""
+    loss: torch.Tensor
+    ce_loss: torch.Tensor
+    z_loss: Optional[torch.Tensor]
+
+
 class LMHeadCEFn(torch.autograd.Function):
+    """Returns the loss; with ``z_loss`` > 0 the triple (objective, cross-entropy, weighted z term), the last two
+    not differentiable."""
+
     @staticmethod
-    def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None, version=0, y8=None):
+    def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None, version=0, y8=None, z_loss=0.0):
         n, d = y.shape
         V = w.shape[0]
         targets = targets.reshape(-1)
@@ -69,6 +94,7 @@ class LMHeadCEFn(torch.autograd.Function):
         scale = (loss_scale / denom).reshape(1).contiguous()
         dy = torch.empty_like(y)
         loss_sum = torch.zeros(1, dtype=torch.float32, device=y.device)
+        z_sum = torch.zeros(1, dtype=torch.float32, device=y.device) if z_loss else None  # sum lse^2, valid rows
         hip = _ext.use_hip(y)
         det = deterministic()
         q = r = None
@@ -87,7 +113,9 @@ class LMHeadCEFn(torch.autograd.Function):
                 rows = torch.empty(e - s, dtype=torch.float32, device=y.device) if det else None
                 dl8 = None
                 t8 = r.target(kdy, E5M2) if q is not None else None
-                if t8 is not None:
+                if z_loss:
+                    dl8 = _ce_z_launch(logits, tc, loss_sum, z_sum, scale, rows, z_loss, t8)
+                elif t8 is not None:
                     # fp8: the CE kernel writes the e5m2 dlogits itself (no bf16 dlogits, no separate cast)
                     q8 = t8.alloc((e - s, V), y.device)
                     rc = _ext.lib().nd_ce_fwd_bwd_q8(_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc),
@@ -98,7 +126,7 @@ class LMHeadCEFn(torch.autograd.Function):
                         dl8 = q8
                     elif rc != _HIP_INVALID_VALUE:  # invalid value = shape not taken: cast separately below
                         _ext.check(rc, "nd_ce_fwd_bwd_q8")
-                if dl8 is None:
+                if dl8 is None and not z_loss:
                     _ext.check(_ext.lib().nd_ce_fwd_bwd(_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc),
                                                         _ext.ptr(loss_sum), _ext.ptr(scale), e - s, V, IGNORE_INDEX,
                                                         0, _ext.ptr(rows) if det else 0, 0.0,
@@ -115,6 +143,9 @@ class LMHeadCEFn(torch.autograd.Function):
                 picked = logits.gather(1, tgt[:, None])[:, 0]
                 loss_sum += torch.where(ok, lse - picked, torch.zeros_like(lse)).sum()
                 p = torch.softmax(logits, dim=-1)
+                if z_loss:
+                    z_sum += torch.where(ok, lse * lse, torch.zeros_like(lse)).sum()
+                    p *= (1.0 + 2.0 * z_loss * lse)[:, None]
                 p.scatter_add_(1, tgt[:, None], -torch.ones_like(p[:, :1]))
                 p *= ok[:, None].to(p.dtype) * scale
                 dl = p.to(y.dtype)
@@ -138,22 +169,71 @@ class LMHeadCEFn(torch.autograd.Function):
                 # side-stream work anyway, ops/linear.py)
                 wgrad_accumulate(gw, dl, yc.to(dl.dtype))
         ctx.save_for_backward(dy)
-        return (loss_sum / denom).reshape(())
+        if not z_loss:
+            return (loss_sum / denom).reshape(())
+        ce = (loss_sum / denom).reshape(())
+        z = (z_sum * z_loss / denom).reshape(())
+        ctx.mark_non_differentiable(ce, z)
+        return ce + z, ce, z
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         (dy,) = ctx.saved_tensors
-        return (dy * g.to(dy.dtype),) + (None,) * 9
+        return (dy * g.to(dy.dtype),) + (None,) * 10
+
+
+def _ce_z_launch(logits, tc, loss_sum, z_sum, scale, rows, z_coef, t8):
+    """The z-loss CE kernel on one chunk of logits; ``rows`` (deterministic mode): per-row cross-entropy, with the
+    per-row lse^2 in a buffer of its own, both summed in order here (no float atomics).  ``t8``: the fp8 target of the
+    dlogits, if any; returns the fp8 dlogits when the q8 entry took the shape, else None (bf16 dlogits in place)."""
+    n, V = logits.shape
+    rows_z = torch.empty_like(rows) if rows is not None else None
+    head = (_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc), _ext.ptr(loss_sum), _ext.ptr(z_sum), _ext.ptr(scale),
+            n, V, IGNORE_INDEX, 0, _ext.ptr(rows), _ext.ptr(rows_z), z_coef)
+    dl8 = None
+    if t8 is not None:
+        q8 = t8.alloc((n, V), logits.device)
+        rc = _ext.lib().nd_ce_z_fwd_bwd_q8(*head, *t8.args(q8), _ext.stream_ptr(logits.device))
+        if rc == 0:
+            dl8 = q8
+        elif rc != _HIP_INVALID_VALUE:  # invalid value = shape not taken: cast separately, as the z-free path
+            _ext.check(rc, "nd_ce_z_fwd_bwd_q8")
+    if dl8 is None:
+        _ext.check(_ext.lib().nd_ce_z_fwd_bwd(*head, _ext.stream_ptr(logits.device)), "nd_ce_z_fwd_bwd")
+    if rows is not None:
+        z_sum += rows_z.sum()
+    return dl8
 
 
 LM_KEY = "x.lm"  # the lm head's slot pair / weight cache in Fp8Linears (ops/fp8.py fp8_projection("lm"))
 
 
+def _z_coef(z_loss) -> float:
+    z = float(z_loss)
+    if not 0.0 <= z < float("inf"):  # refuses NaN too
+        raise ValueError(f"z_loss must be a finite coefficient >= 0 (0 = off), got {z_loss!r}")
+    return z
+
+
 def lm_head_ce(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torch.Tensor, loss_scale: float = 1.0,
-               chunk_rows: int = 0, wt: torch.Tensor = None, f8=None, version: int = 0, y8=None) -> torch.Tensor:
+               chunk_rows: int = 0, wt: torch.Tensor = None, f8=None, version: int = 0, y8=None,
+               z_loss: float = 0.0) -> torch.Tensor:
     """``wt``: optional W^T copy [d, V] for the input-gradient GEMM (see ops/linear.py).  ``f8``: the model's
-    ``Fp8Linears`` for the fp8 lm head, with the weight ``version`` and ``y8``, the fused e4m3 copy of y if any."""
-    return LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8, int(version), y8)
+    ``Fp8Linears`` for the fp8 lm head, with the weight ``version`` and ``y8``, the fused e4m3 copy of y if any.
+    ``z_loss``: the z-loss coefficient (0.0 = off); the returned loss is the objective, cross-entropy + z term."""
+    return lm_head_ce_parts(y, w, gw, targets, loss_scale, chunk_rows, wt, f8, version, y8, z_loss).loss
+
+
+def lm_head_ce_parts(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torch.Tensor,
+                     loss_scale: float = 1.0, chunk_rows: int = 0, wt: torch.Tensor = None, f8=None, version: int = 0,
+                     y8=None, z_loss: float = 0.0) -> LMHeadLoss:
+    """``lm_head_ce`` with the objective's two parts beside it (``LMHeadLoss``)."""
+    z = _z_coef(z_loss)
+    if z == 0.0:  # today's call, argument for argument
+        loss = LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8, int(version), y8)
+        return LMHeadLoss(loss, loss.detach(), None)
+    return LMHeadLoss(*LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8, int(version),
+                                        y8, z))
 
 
 @torch.no_grad()

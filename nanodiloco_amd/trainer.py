@@ -61,6 +61,9 @@ class TrainArgs:
     outer_momentum: float = 0.9
     max_grad_norm: float = 1.0
     weight_decay: float = 0.01
+    z_loss: float = 0.0            # z-loss coefficient: the objective gains z_loss * mean(logsumexp(logits)^2) inside
+                                   # the lm-head CE kernels (docs/DESIGN.md "z-loss"); 0 = off.  The logged `loss`
+                                   # stays the cross-entropy, the weighted term is logged as `z_loss`
     inner_optimizer: str = "adamw"  # adamw | muon: Muon ("MuLoCo") on the decoder projection weights, AdamW on the
                                     # rest (optim.FlatMuon, docs/DESIGN.md "Muon inner optimizer")
     muon_momentum: float = 0.95
@@ -207,6 +210,8 @@ class Trainer:
         self.args = a = args
         if a.total_steps % a.inner_steps:
             raise ValueError("total_steps must be a multiple of inner_steps")  # REF main.py:69
+        if not 0.0 <= a.z_loss < float("inf"):  # NaN fails both comparisons
+            raise ValueError(f"--z-loss must be a finite coefficient >= 0 (0 = off), got {a.z_loss}")
         if a.comm_topk:
             if not 1 <= a.comm_topk <= 4096:
                 raise ValueError(f"--comm-topk must be in [1, 4096] entries per chunk of 4096 (0 = off), got {a.comm_topk}")
@@ -251,6 +256,8 @@ class Trainer:
                                       fp8=a.fp8 or a.dtype == "fp8", fp8_wgrad=a.fp8_wgrad,
                                       residual_dtype=_residual_dtype(a.residual_dtype, a.fp8 or a.dtype == "fp8"),
                                       doc_mask=a.doc_mask).init_weights(a.seed)
+        self.model.z_loss = float(a.z_loss)
+        self.last_z_loss = None  # --z-loss: the last inner step's weighted z term, mean over micro-batches (device)
         if a.inner_optimizer == "muon":
             if e.device.type == "cuda" and ops.get_backend() != "torch":
                 raise ValueError("--inner-optimizer muon has no HIP kernels yet: on a GPU it needs --ops torch "
@@ -344,8 +351,10 @@ class Trainer:
 
     # ------------------------------------------------------------------ one inner step
     def inner_step(self) -> torch.Tensor:
-        """grad_accum micro-batches fwd+bwd, inner-DDP sync, clip+AdamW. Returns mean loss (device)."""
-        loss_sum = None
+        """grad_accum micro-batches fwd+bwd, inner-DDP sync, clip+AdamW. Returns mean loss (device): the
+        cross-entropy; with --z-loss the weighted z term of the objective is left in ``last_z_loss``."""
+        loss_sum = z_sum = None
+        z_on = self.model.z_loss > 0
         with self.timer.phase("fwd_bwd"):
             for micro in range(self.grad_accum):
                 batch = next(self.data)
@@ -354,15 +363,23 @@ class Trainer:
                 mask = batch.get("attention_mask")  # HF path: padded batches (reference main.py:79-88,109)
                 if self.graphed is not None and mask is None:
                     l = self.graphed(batch["input_ids"], batch["labels"], self.loss_scale).clone()
+                    if z_on:  # the graph's static outputs: copied before the next replay
+                        l, z = self.graphed.ce_loss.clone(), self.graphed.z_loss.clone()
                 else:
                     out = self.model(batch["input_ids"], labels=batch["labels"], attention_mask=mask,
                                      loss_scale=self.loss_scale)
                     out.loss.backward()
                     l = out.loss.detach()
+                    if z_on:
+                        l, z = out.ce_loss, out.z_loss
                 loss_sum = l if loss_sum is None else loss_sum + l
+                if z_on:
+                    z_sum = z if z_sum is None else z_sum + z
         with self.timer.phase("inner_opt"):
             self.inner_sync.finish()
             self.diloco.inner_step()
+        if z_on:
+            self.last_z_loss = z_sum / self.grad_accum
         return loss_sum / self.grad_accum
 
     def evaluate(self, step: Optional[int] = None) -> Dict[str, Any]:
@@ -424,6 +441,8 @@ class Trainer:
                     "grad_norm": float(self.diloco.inner_optimizer.last_grad_norm.item()),
                     "outer_step": self.diloco.outer_step_count,
                 }
+                if a.z_loss > 0:
+                    metrics["z_loss"] = float(self.last_z_loss.item())
                 if a.skip_nonfinite:
                     metrics["skipped_steps"] = int(self.diloco.inner_optimizer.skipped_steps.item())
                 if frag_event is not None:

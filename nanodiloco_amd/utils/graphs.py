@@ -7,7 +7,8 @@ host syncs (the loss scale, token counts and clip coefficients live in device me
 kernel launched on the current stream, gradients accumulated in place into the flat grad buffer
 -- so after two eager warm-up calls (side stream, as torch.cuda.graphs requires) the forward +
 backward is captured once into a HIP graph and each later micro-batch is one ``graph.replay()``
-after copying the new token ids into the graph's static input buffers.
+after copying the new token ids into the graph's static input buffers.  The loss and its two parts (cross-entropy
+and, with z-loss, the weighted z term) come back through the graph's static output buffers.
 
 Not captured: the optimizer step (its learning rate / bias corrections are host scalars that change
 every step), the outer DiLoCo step and its collectives, and the inner-DDP gradient hooks (the
@@ -30,12 +31,17 @@ class GraphedMicroStep:
         self.calls = 0
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.ids = self.labels = self.loss = None
-        self.loss_scale = None
+        # the parts of the last call's loss (CausalLMOutput.ce_loss / .z_loss; z_loss None unless model.z_loss > 0).
+        # After capture they are the graph's static outputs, like the returned loss: valid until the next call
+        self.ce_loss = self.z_loss = None
+        self._static = None  # (loss, ce_loss, z_loss) the captured graph writes
+        self.loss_scale = self.z_coef = None
         self.eager_fallbacks = 0
 
     def _run(self, ids, labels, loss_scale):
         out = self.model(ids, labels=labels, loss_scale=loss_scale)
         out.loss.backward()
+        self.ce_loss, self.z_loss = out.ce_loss, out.z_loss
         return out.loss.detach()
 
     def __call__(self, ids: torch.Tensor, labels: torch.Tensor, loss_scale: float = 1.0) -> torch.Tensor:
@@ -52,16 +58,21 @@ class GraphedMicroStep:
             return self._run(ids, labels, loss_scale)
         if self.graph is None:
             self.ids, self.labels, self.loss_scale = ids.clone(), labels.clone(), loss_scale
+            self.z_coef = self.model.z_loss
             self.model.refresh_transposed()  # nothing stale gets captured as a copy
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):  # records only; the replay below does the work
                 self.loss = self._run(self.ids, self.labels, loss_scale)
+            self._static = (self.loss, self.ce_loss, self.z_loss)
         if loss_scale != self.loss_scale:
             raise ValueError("loss_scale changed after capture")
+        if self.model.z_loss != self.z_coef:  # a kernel argument of the captured launches
+            raise ValueError("model.z_loss changed after capture")
         self.model.refresh_transposed()  # W^T copies the captured dgrad GEMMs read
         self.ids.copy_(ids, non_blocking=True)
         self.labels.copy_(labels, non_blocking=True)
         self.graph.replay()
+        self.loss, self.ce_loss, self.z_loss = self._static  # (an eager fallback in between replaced them)
         return self.loss
 
 
