@@ -18,6 +18,8 @@ from .muon import ns_gram, ns_poly, ns_update, ns_iterate, newton_schulz, muon_s
     MuonPlan, AdamWSpans
 from .qcomm import pseudograd_q, qreduce, outer_nesterov_q, pseudograd_q_ef, qreduce_ef
 from .sparse_comm import pseudograd_topk, outer_nesterov_topk, topk_slot_bytes, densify
+from .lowrank_comm import LowRankPlan, lowrank_project, lowrank_orthonormalize, lowrank_backproject, \
+    outer_nesterov_lowrank, lowrank_wire_elems
 from .determinism import set_deterministic, deterministic
 from . import reference
 
@@ -29,5 +31,6 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "lm_head_ce", "lm_head_ce_parts", "LMHeadLoss", "lm_head_loss",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
            "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "pseudograd_topk", "outer_nesterov_topk",
-           "topk_slot_bytes", "densify","frag_pseudograd", "frag_outer_mix", "SpanTable", "reference",
+           "topk_slot_bytes", "densify", "LowRankPlan", "lowrank_project", "lowrank_orthonormalize",
+           "lowrank_backproject", "outer_nesterov_lowrank", "lowrank_wire_elems", "frag_pseudograd", "frag_outer_mix", "SpanTable", "reference",
            "ns_gram", "ns_poly", "ns_update", "ns_iterate", "newton_schulz", "muon_step", "adamw_step_spans", "MuonPlan", "AdamWSpans"]

@@ -193,6 +193,11 @@ def _declare(L: ctypes.CDLL):
         # top-k sparse outer transport (csrc/sparse_comm.hip)
         "nd_pseudograd_topk": [P, P, P, L64, P, I, I, P],
         "nd_outer_nesterov_topk": [P, P, P, I, I, I, P, P, I, L64, F, F, F, I, P],
+        # low-rank (PowerSGD) outer transport (csrc/lowrank_comm.hip): host and device copies of the tables
+        "nd_lowrank_project": [P, P, P, P, P, P, P, I, P, P, I, I, L64, L64, L64, P],
+        "nd_lowrank_orthonormalize": [P, P, P, I, I, L64, P],
+        "nd_lowrank_backproject": [P, P, P, P, P, I, I, L64, L64, L64, P],
+        "nd_outer_nesterov_lowrank": [P, P, P, P, P, P, P, P, P, I, P, P, P, I, P, P, I, I, L64, L64, L64, F, F, F, I, P],
         # fp8 quantisation
         "nd_fp8_cast":[P, I, L64, P, P, I, P, I, P],
         "nd_fp8_cast_t": [P, I, I, I, L64, P, P, P, I, P, I, P],

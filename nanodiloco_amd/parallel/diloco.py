@@ -15,7 +15,7 @@ pseudo-gradient.  Capability parity with ``class Diloco`` (REF/nanodiloco/diloco
   avg_sync_time always 0 (:62-64, dead)          real: wall time of every outer step (host) and
                                                  device time of its collectives (HIP events)
 
-Extensions (north star).  How the pseudo-gradient travels is one of four transports
+Extensions (north star).  How the pseudo-gradient travels is one of five transports
 (``parallel/transports.py``, whose classes document the protocols); :func:`_check_options` has every rule
 about which options go together:
 * ``comm_dtype`` fp32 / bf16 (half the bytes / outer step), ``overlap=True`` (the DELAYED outer update: one
@@ -27,6 +27,8 @@ about which options go together:
   :meth:`Diloco.stream_step`: :class:`~.transports.StreamingTransport`;
 * ``topk=K`` (--comm-topk; ``comm_dtype`` fp32 / bf16 is then the dtype of the values sent): the K largest entries
   of every 4096-element chunk travel, the rest waits in an fp32 residual: :class:`~.transports.TopKTransport`;
+* ``lowrank=R`` (--comm-rank; PowerSGD): every large enough matrix travels as two all-reducible factors of R columns,
+  what they did not carry waits in an fp32 residual: :class:`~.transports.LowRankTransport`;
 * ``inner_dp > 1`` (two-level): the W/K workers' outer all-reduce is sharded over the K GPUs of a
   worker (each reduces 1/K of the pseudo-gradient over its outer group, then the worker
   all-gathers the updated weights), so cross-worker bytes per GPU drop by K.
@@ -44,15 +46,19 @@ from .comm import FlatCommunicator
 from .dist import DistEnv
 from .fragments import PATTERNS
 from ..ops.sparse_comm import CHUNK as TOPK_CHUNK
-from .transports import DenseTransport, QuantisedTransport, StepTimer, StreamingTransport, TopKTransport
+from ..ops.lowrank_comm import MAX_RANK as LOWRANK_MAX
+from .transports import DenseTransport, LowRankTransport, QuantisedTransport, StepTimer, StreamingTransport, \
+    TopKTransport
 from .transports import quantised_bits  # also the name existing imports of it use
 
 
 def _check_options(flat_store: bool, comm_dtype=torch.float32, overlap=False, offload_snapshot=False, inner_dp=1,
                    error_feedback=False, fragments=0, fragment_pattern="strided", stream_overlap=0, stream_alpha=0.0,
-                   num_layers=0, inner_steps=0, topk=0) -> int:
+                   num_layers=0, inner_steps=0, topk=0, lowrank=0) -> int:
     """Every rule about which options go together, checked before a transport exists.  Returns the bits of
     the quantised transport (0: fp32 / bf16)."""
+    if lowrank:
+        _check_lowrank(flat_store, comm_dtype, overlap, error_feedback, fragments, topk, inner_dp, lowrank)
     if topk:
         _check_topk(flat_store, comm_dtype, overlap, error_feedback, fragments, topk)
     if not flat_store:
@@ -109,6 +115,26 @@ def _check_topk(flat_store: bool, comm_dtype, overlap, error_feedback, fragments
             raise ValueError(f"top-k sparse transport (topk > 0, --comm-topk) is not supported together with {what}")
 
 
+def _check_lowrank(flat_store: bool, comm_dtype, overlap, error_feedback, fragments, topk, inner_dp, lowrank) -> None:
+    """The rules of the low-rank transport (``lowrank`` > 0, --comm-rank)."""
+    if not flat_store:
+        raise ValueError("low-rank transport (lowrank > 0, --comm-rank) needs the flat-store Llama of Diloco: "
+                         "ModuleDiloco does not take it")
+    if not 1 <= int(lowrank) <= LOWRANK_MAX:
+        raise ValueError(f"lowrank (--comm-rank) must be in [1, {LOWRANK_MAX}] columns per factor, got {lowrank}")
+    if comm_dtype != torch.float32:
+        raise ValueError(f"low-rank transport (lowrank > 0, --comm-rank) sends fp32 factors, not comm_dtype "
+                         f"{comm_dtype}: bf16 or quantised factors are not implemented")
+    for on, what in ((error_feedback, "error_feedback=True (--comm-error-feedback): low-rank always carries its own "
+                                      "residual, and that flag belongs to the quantised transport"),
+                     (bool(topk), "the top-k sparse transport (topk > 0, --comm-topk)"),
+                     (overlap, "overlap=True (--overlap-outer)"),
+                     (bool(fragments), "Streaming DiLoCo (fragments > 0, --streaming-fragments)"),
+                     (inner_dp > 1, "inner_dp > 1 (--inner-dp): the shards of a worker cut matrices")):
+        if on:
+            raise ValueError(f"low-rank transport (lowrank > 0, --comm-rank) is not supported together with {what}")
+
+
 class Diloco:
     """Flagship DiLoCo on the flat-store Llama.  Any other ``nn.Module`` (with plain torch optimizers)
     is dispatched to :class:`~nanodiloco_amd.parallel.module_diloco.ModuleDiloco`, which has the
@@ -118,7 +144,7 @@ class Diloco:
         if not isinstance(model, LlamaForCausalLM):
             from .module_diloco import ModuleDiloco
             _check_options(False, fragments=kwargs.get("fragments"), error_feedback=kwargs.pop("error_feedback", False),
-                           topk=kwargs.pop("topk", 0))
+                           topk=kwargs.pop("topk", 0), lowrank=kwargs.pop("lowrank", 0))
             return ModuleDiloco(model, *args, **kwargs)
         return super().__new__(cls)
 
@@ -128,7 +154,8 @@ class Diloco:
                  env: Optional[DistEnv] = None, comm_dtype: torch.dtype = torch.float32, bucket_mb: float = 128.0,
                  overlap: bool = False, offload_snapshot: bool = False, debug_checks: bool = False,
                  broadcast_init: bool = True, fragments: int = 0, fragment_pattern: str = "strided",
-                 stream_overlap: int = 0, stream_alpha: float = 0.0, error_feedback: bool = False, topk: int = 0):
+                 stream_overlap: int = 0, stream_alpha: float = 0.0, error_feedback: bool = False, topk: int = 0,
+                 lowrank: int = 0):
         self.model = model
         self.store = model.store
         self.inner_optimizer = inner_optimizer
@@ -147,9 +174,10 @@ class Diloco:
         self.stream_overlap = int(stream_overlap)
         self.stream_alpha = float(stream_alpha)
         self.topk = int(topk)
+        self.lowrank = int(lowrank)
         qbits = _check_options(True, comm_dtype, overlap, offload_snapshot, self.env.inner_dp, error_feedback,
                                self.fragments, fragment_pattern, self.stream_overlap, self.stream_alpha,
-                               model.config.num_hidden_layers, inner_steps, self.topk)
+                               model.config.num_hidden_layers, inner_steps, self.topk, self.lowrank)
         e = self.env
         f = e.force_collectives
         kw = dict(impl=e.comm_impl, device=e.device, timeout_s=e.timeout_s)
@@ -178,7 +206,9 @@ class Diloco:
         self.local_step = 0
         self.outer_step_count = 0
         # ---- the one place that tells the transports apart
-        if self.topk:
+        if self.lowrank:
+            self.transport = LowRankTransport(self, self.lowrank)
+        elif self.topk:
             self.transport = TopKTransport(self, self.topk, comm_dtype)
         elif qbits:
             self.transport = QuantisedTransport(self, qbits, self.error_feedback)
@@ -227,7 +257,7 @@ class Diloco:
         return self.scheduler.lr()
 
     _TRANSPORT_NAMES = ("delta", "qbits", "qef_send", "qef_reduce", "error_feedback_state", "frag_tables", "frag_steps",
-                        "fragment_sync_count", "topk_residual")
+                        "fragment_sync_count", "topk_residual", "lowrank_residual", "lowrank_q")
 
     def __getattr__(self, name):
         """Read-only forwards of the active transport's public state (absent where that transport has none)."""

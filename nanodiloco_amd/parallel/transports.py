@@ -1,4 +1,4 @@
-"""The four ways :class:`~nanodiloco_amd.parallel.diloco.Diloco` moves its pseudo-gradient.  Each transport owns
+"""The five ways :class:`~nanodiloco_amd.parallel.diloco.Diloco` moves its pseudo-gradient.  Each transport owns
 its wire buffers, its protocol and the part of a checkpoint that only it understands; ``Diloco`` builds exactly
 one (``Diloco.transport``) and keeps what does not depend on it: the snapshot, the counters, the communicators,
 ``_after_update`` and the :class:`StepTimer`.
@@ -7,7 +7,8 @@ What ``Diloco`` and ``utils/checkpoint.py`` ask of a transport: ``bytes_per_step
 ``finalize()``, ``local_weights_differ``, and for checkpoints ``rank_state() -> (tensors, scalars)`` (this rank's
 files), ``shared_state() -> (trainer_state.json entries, config.json flags)`` and ``load_state(per, scal, shared)
 -> lines to log`` (``per`` / ``scal``: this rank's OWN files, empty for a worker the checkpoint did not have).
-Dense, quantised and top-k run ``step(phases)``; streaming runs ``stream_step(t)`` and ``flush()``.
+A transport may also have ``shared_tensors()``, saved once for all workers.  Dense, quantised, top-k and low-rank run
+``step(phases)``; streaming runs ``stream_step(t)`` and ``flush()``.
 """
 from __future__ import annotations
 
@@ -17,12 +18,14 @@ from typing import Optional
 import torch
 
 from .. import ops
-from ..ops import qcomm, sparse_comm
+from ..ops import lowrank_comm, qcomm, sparse_comm
 from .comm import PendingAllReduce, plan_buckets
 from .fragments import fragment_due, plan_fragments
 
 _EF_IGNORED = "checkpoint holds error-feedback residuals; this run has no --comm-error-feedback: ignored"
 _TOPK_IGNORED = "checkpoint holds a top-k residual (topk.residual); this run has no --comm-topk: ignored"
+_LOWRANK_IGNORED = ("checkpoint holds low-rank transport state (lowrank.residual, lowrank.q); this run has no "
+                    "--comm-rank: ignored")
 
 
 def quantised_bits(comm_dtype) -> int:
@@ -105,13 +108,19 @@ class Transport:
     def shared_state(self):
         return {"pending_outer": False}, {}
 
+    def shared_tensors(self):
+        """Tensors that are identical on every worker and belong to this transport: rank 0 writes them next to
+        theta_sync (``diloco_state.safetensors``), and ``load_state`` finds them in ``shared`` under their names."""
+        return {}
+
     def load_state(self, per, scal, shared) -> list:
         if shared.get("pending_outer"):
             raise RuntimeError("checkpoint holds a pending overlapped outer step: resume with --overlap-outer")
         if self.d is not None and self.d.env.rank != 0:
             return []
         return ([_EF_IGNORED] if "qef.send" in per or "qef.reduce" in per else []) + \
-            ([_TOPK_IGNORED] if "topk.residual" in per else [])
+            ([_TOPK_IGNORED] if "topk.residual" in per else []) + \
+            ([_LOWRANK_IGNORED] if "lowrank.residual" in per else [])
 
 
 class DenseTransport(Transport):
@@ -378,8 +387,8 @@ class QuantisedTransport(Transport):
         return {"pending_outer": False, **feedback}, {}
 
     def load_state(self, per, scal, shared) -> list:
-        # refuses a pending overlapped step; a top-k residual is not this transport's
-        other = super().load_state({k: v for k, v in per.items() if k.startswith("topk.")}, scal, shared)
+        # refuses a pending overlapped step; a top-k or low-rank residual is not this transport's
+        other = super().load_state({k: v for k, v in per.items() if k.startswith(("topk.", "lowrank."))}, scal, shared)
         send, reduce, saved = per.get("qef.send"), per.get("qef.reduce"), shared.get("comm_error_feedback")
         had = saved is not None or send is not None
         if not (had or self.error_feedback):
@@ -488,7 +497,7 @@ class TopKTransport(Transport):
         """The residual is an fp32 amount still owed, indexed by element of the owned span: restored whenever its
         length matches -- k, the value dtype and the number of workers may differ --, else zero.  A rank without
         one (a checkpoint of another transport, a worker the checkpoint did not have) starts at zero."""
-        lines = super().load_state({k: v for k, v in per.items() if k.startswith("qef.")}, scal, shared)
+        lines = super().load_state({k: v for k, v in per.items() if k.startswith(("qef.", "lowrank."))}, scal, shared)
         saved = per.get("topk.residual")
         self.residual.zero_()
         if saved is None:
@@ -499,6 +508,116 @@ class TopKTransport(Transport):
         else:
             lines.append(f"topk.residual has {saved.numel()} elements, this rank owns {self.residual.numel()}: "
                          f"starting from zero")
+        return lines
+
+
+class LowRankTransport(Transport):
+    """Low-rank (PowerSGD) transport with error feedback (``ops/lowrank_comm.py``, docs/DESIGN.md §4): every 2-D
+    tensor [m, n] with ``min(m, n) >= 4 R`` and ``n % 4 == 0`` travels as two factors P [m, R] and Q [n, R], the rest
+    (norm weights, small or odd matrices) as plain fp32.  The factors are linear in the pseudo-gradient, so both are
+    all-reduced and the bytes sent and received do not depend on the number of workers.  The step is
+    ``nd_lowrank_project`` -> all-reduce of ``[dense | all P]`` -> ``nd_lowrank_orthonormalize`` ->
+    ``nd_lowrank_backproject`` -> all-reduce of ``[all Q]`` -> ``nd_outer_nesterov_lowrank``; everything after an
+    all-reduce is computed by deterministic kernels from identical bytes, so theta_sync and the master stay
+    bit-identical across workers.  ``residual`` (fp32, one element per element, zero on the dense spans) is this
+    rank's checkpoint state (``lowrank.residual``); ``q`` is identical on every worker and is saved once
+    (``lowrank.q``); Q0 is regenerated from a constant seed and never saved."""
+
+    def __init__(self, diloco, rank: int):
+        super().__init__(diloco)
+        store = diloco.store
+        dev = store.device
+        self.rank = int(rank)
+        self.plan = lowrank_comm.LowRankPlan.from_store(store, self.rank)
+        if not len(self.plan):
+            raise ValueError(f"low-rank transport (lowrank > 0, --comm-rank): no tensor of this model is a matrix "
+                             f"with min(m, n) >= 4 * {self.rank} and n % 4 == 0, so there is nothing to compress")
+        self.residual = torch.zeros(store.numel, dtype=torch.float32, device=dev)
+        self.q0 = self.plan.init_q().to(dev)
+        self.q = self.q0.clone()
+        w1, w2 = lowrank_comm.lowrank_wire_elems(self.plan)
+        self.wire1 = torch.zeros(w1, dtype=torch.float32, device=dev)
+        self.wire2 = torch.zeros(w2, dtype=torch.float32, device=dev)
+
+    @property
+    def lowrank_residual(self) -> torch.Tensor:
+        return self.residual
+
+    @property
+    def lowrank_q(self) -> torch.Tensor:
+        return self.q
+
+    @property
+    def bytes_per_step(self) -> int:
+        """both rounds: ``[dense | all P]`` and ``[all Q]``, fp32"""
+        return 4 * (self.wire1.numel() + self.wire2.numel())
+
+    @property
+    def buckets_per_step(self) -> int:
+        bb = self.d.outer_comm.bucket_bytes
+        return len(plan_buckets(0, self.wire1.numel(), 4, bb)) + len(plan_buckets(0, self.wire2.numel(), 4, bb))
+
+    def step(self, phases: bool):
+        """Two all-reduce rounds, each waited for before the kernel that reads it (the rounds do not overlap each
+        other yet).  With ``phases`` the collective span also holds the orthonormalisation and the back-projection
+        that sit between the two rounds."""
+        d, timer = self.d, self.d.timer
+        ev0, t0 = timer.start(phases)
+        sync = d._sync_on_device()
+        opt = d.outer_optimizer
+        master, mom = d.store.master, opt.momentum_buffer
+        sh_full = d.store.separate_shadow
+        ops.lowrank_project(sync, master, self.residual, self.q, self.wire1, self.plan)
+        timer.phase()
+        d.outer_comm.all_reduce_async(self.wire1).wait_all()
+        ops.lowrank_orthonormalize(self.wire1, self.plan)
+        ops.lowrank_backproject(self.residual, self.wire1, self.wire2, self.plan)
+        d.outer_comm.all_reduce_async(self.wire2).wait_all()
+        timer.phase()
+        d.outer_step_count += 1
+        ops.outer_nesterov_lowrank(master, sync, self.residual, self.wire1, self.wire2, self.q, self.q0, mom, sh_full,
+                                   self.plan, 1.0 / max(1, d.env.num_workers), opt.lr, opt.momentum,
+                                   opt.step_count == 0)
+        d._after_update(sync, sh_full, ev0, t0)
+
+    def rank_state(self):
+        return {"lowrank.residual": self.residual}, {}
+
+    def shared_state(self):
+        return {"pending_outer": False, "comm_lowrank": {"rank": self.rank, "seed": lowrank_comm.Q_SEED}}, {}
+
+    def shared_tensors(self):
+        return {"lowrank.q": self.q}
+
+    def load_state(self, per, scal, shared) -> list:
+        """The residual is an fp32 amount still owed, indexed by element: restored whenever its length matches --
+        the rank may differ --, else zero.  Q is restored when the saved rank, seed and length equal this run's (the
+        table follows from the model and the rank), else it starts from Q0 again.  Q is the same on every worker, so
+        what concerns it is rank 0's to log."""
+        lines = super().load_state({k: v for k, v in per.items() if k.startswith(("qef.", "topk."))}, scal, shared)
+        meta, first = shared.get("comm_lowrank"), self.d.env.rank == 0
+        same = meta is not None and int(meta.get("rank", -1)) == self.rank \
+            and int(meta.get("seed", -1)) == lowrank_comm.Q_SEED
+        saved = per.get("lowrank.residual")
+        self.residual.zero_()
+        if saved is None:
+            if meta is not None:  # the checkpoint had residuals, this rank has none in it
+                lines.append("no low-rank residual in the checkpoint for this rank: starting from zero")
+        elif saved.numel() == self.residual.numel():
+            self.residual.copy_(saved)
+            if not same and first:
+                lines.append(f"lowrank.residual was left by rank {meta.get('rank') if meta else '?'}, this run has "
+                             f"rank {self.rank}: kept, it is an amount still owed")
+        else:
+            lines.append(f"lowrank.residual has {saved.numel()} elements, this rank owns {self.residual.numel()}: "
+                         f"starting from zero")
+        qs = shared.get("lowrank.q")
+        self.q.copy_(self.q0)
+        if same and qs is not None and qs.numel() == self.q.numel():
+            self.q.copy_(qs)
+        elif meta is not None and first:
+            lines.append(f"lowrank.q was saved for rank {meta.get('rank')}, this run has rank {self.rank}: "
+                         f"re-seeded from the constant seed")
         return lines
 
 

@@ -74,6 +74,9 @@ class TrainArgs:
     comm_topk: int = 0             # K > 0: top-k sparse outer transport -- of every 4096-element chunk only the K
                                    # largest entries travel (values in --comm-dtype fp32 | bf16), the rest waits in
                                    # an fp32 residual (docs/DESIGN.md "Top-k sparse transport"); 0 = off
+    comm_rank: int = 0             # R > 0: low-rank (PowerSGD) outer transport -- every matrix with min(m, n) >= 4 R
+                                   # travels as two all-reduced fp32 factors of R columns, the rest waits in an fp32
+                                   # residual (docs/DESIGN.md "Low-rank transport"); 0 = off
     bucket_mb: float = 128.0
     overlap_outer: bool = False
     offload_snapshot: bool = False
@@ -212,6 +215,17 @@ class Trainer:
             raise ValueError("total_steps must be a multiple of inner_steps")  # REF main.py:69
         if not 0.0 <= a.z_loss < float("inf"):  # NaN fails both comparisons
             raise ValueError(f"--z-loss must be a finite coefficient >= 0 (0 = off), got {a.z_loss}")
+        if a.comm_rank:
+            if not 1 <= a.comm_rank <= 32:
+                raise ValueError(f"--comm-rank must be in [1, 32] columns per factor (0 = off), got {a.comm_rank}")
+            for on, what in ((a.comm_dtype != "fp32", f"--comm-dtype {a.comm_dtype}: the factors travel as fp32"),
+                             (a.comm_error_feedback, "--comm-error-feedback: low-rank always carries its own residual"),
+                             (a.comm_topk > 0, "--comm-topk"),
+                             (a.overlap_outer, "--overlap-outer"),
+                             (a.streaming_fragments > 0, "--streaming-fragments"),
+                             (a.inner_dp > 1, "--inner-dp > 1: the shards of a worker cut matrices")):
+                if on:
+                    raise ValueError(f"--comm-rank is not supported together with {what}")
         if a.comm_topk:
             if not 1 <= a.comm_topk <= 4096:
                 raise ValueError(f"--comm-topk must be in [1, 4096] entries per chunk of 4096 (0 = off), got {a.comm_topk}")
@@ -277,7 +291,7 @@ class Trainer:
                              debug_checks=a.debug_checks, fragments=a.streaming_fragments,
                              fragment_pattern=a.streaming_pattern, stream_overlap=a.streaming_overlap_steps,
                              stream_alpha=a.streaming_alpha, error_feedback=a.comm_error_feedback,
-                             topk=a.comm_topk)
+                             topk=a.comm_topk, lowrank=a.comm_rank)
         if a.streaming_fragments and a.elastic_resume:
             raise ValueError("--elastic-resume is not supported with --streaming-fragments: a streaming checkpoint "
                              "holds per-worker local weights")

@@ -47,6 +47,13 @@ residual is an amount still owed, whatever it was selected with: it is restored 
 another value dtype, another number of workers), else the rank starts from zero with a logged line; a rank without one
 starts at zero, and a run without ``--comm-topk`` ignores it with a logged line (``TopKTransport.load_state``).
 
+With ``--comm-rank R`` (low-rank transport) every rank file carries ``lowrank.residual`` (fp32, one element per element
+of the flat vector, zero on the dense spans), ``diloco_state.safetensors`` carries ``lowrank.q`` (the Q factors, the same
+on every worker: ``transport.shared_tensors()``) and ``trainer_state.json`` records ``comm_lowrank: {rank, seed}``.  The
+residual is restored whenever its length matches, also under another R (logged); Q only when R and the seed are the
+checkpoint's, else it is re-seeded (logged) -- Q0 is regenerated from the seed and never saved; a run without
+``--comm-rank`` ignores both with a logged line (``LowRankTransport.load_state``).
+
 Crash consistency (round 5): every rank writes into ``<dir>.tmp``; after a barrier rank 0 adds
 ``COMPLETE.json`` and swaps the staging directory in (``<dir>`` -> ``<dir>.old``, ``<dir>.tmp`` -> ``<dir>``,
 then ``<dir>.old`` is removed), so a crash at any point of a save leaves the previous complete checkpoint
@@ -162,7 +169,8 @@ def save_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, step: int, data_
         _save_st(os.path.join(ckpt_dir, "model.safetensors"), {n: store.master_view(n) for n in store.names})
         sync = diloco.sync.to(store.device) if diloco.sync.device != store.device else diloco.sync
         _save_st(os.path.join(ckpt_dir, "diloco_state.safetensors"),
-                 {"theta_sync": sync, "outer_momentum": diloco.outer_optimizer.momentum_buffer})
+                 {"theta_sync": sync, "outer_momentum": diloco.outer_optimizer.momentum_buffer,
+                  **diloco.transport.shared_tensors()})
         state = {"step": step, "local_step": diloco.local_step, "outer_step_count": diloco.outer_step_count,
                  "outer_opt_step": diloco.outer_optimizer.step_count, "scheduler": diloco.scheduler.state_dict(),
                  "world_size": env.world_size, "inner_dp": env.inner_dp, "flat_numel": store.numel,
@@ -269,7 +277,8 @@ def load_checkpoint(ckpt_dir: str, model, diloco, env: DistEnv, elastic: bool = 
             for k, v in scal.items():
                 if k.startswith("data."):
                     data_state[k[5:]] = v
-    for line in diloco.transport.load_state(t_per, t_scal, state):
+    shared_t = {k: v for k, v in ds.items() if k not in ("theta_sync", "outer_momentum")}  # transport.shared_tensors()
+    for line in diloco.transport.load_state(t_per, t_scal, {**state, **shared_t}):
         print(f"[resume] rank {env.rank}: {line}", flush=True)
     state["data_state"] = data_state
     if resized:
