@@ -1,6 +1,7 @@
 """Multi-process CPU harness: W gloo ranks on 127.0.0.1 via torch.multiprocessing."""
 import os
 import socket
+import time
 import traceback
 
 import torch.multiprocessing as mp
@@ -41,19 +42,39 @@ def _entry(rank, world, port, fn, args, q):
             dist.destroy_process_group()
 
 
-def run_ranks(fn, world, *args, timeout=300):
+def _end(procs):
+    """Kill the ranks and wait until they are gone (a killed process may still hold its device)."""
+    for p in procs:
+        p.kill()
+    for p in procs:
+        p.join(30)
+
+
+def _get(q, procs, deadline):
+    """The next report; with a ``deadline`` a child that died without one or ran past it ends the run (all killed)."""
+    while deadline is not None and q.empty():
+        dead = [p.pid for p in procs if p.exitcode not in (None, 0)]
+        if dead or time.monotonic() > deadline:
+            _end(procs)
+            raise AssertionError(f"children {dead} died without a report" if dead else "the ranks ran past their time limit")
+        time.sleep(0.02)
+    return q.get()
+
+
+def run_ranks(fn, world, *args, timeout=300, limit=None):
+    """``limit``: seconds all ranks together may take (GPU children: nothing may go on after a rank hung or died)."""
     ctx = mp.get_context("spawn")
     q = ctx.SimpleQueue()
     port = free_port()
     procs = [ctx.Process(target=_entry, args=(r, world, port, fn, args, q)) for r in range(world)]
     for p in procs:
         p.start()
+    deadline = time.monotonic() + limit if limit is not None else None
     out = {}
     for _ in range(world):
-        r, st, res = q.get()
+        r, st, res = _get(q, procs, deadline)
         if st != "ok":
-            for p in procs:
-                p.kill()
+            _end(procs)
             raise AssertionError(f"rank {r} failed:\n{res}")
         out[r] = res
     for p in procs:

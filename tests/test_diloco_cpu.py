@@ -8,6 +8,7 @@ from nanodiloco_amd.optim import FlatAdamW, FlatOuterNesterov
 from nanodiloco_amd.parallel.diloco import Diloco
 from nanodiloco_amd.parallel.dist import init_distributed
 
+from . import _outer_chains as oc
 from ._mp import run_ranks
 
 TINY = dict(hidden_size=32, intermediate_size=64, num_attention_heads=2, num_hidden_layers=1, vocab_size=50,
@@ -53,25 +54,8 @@ def test_golden_values_two_workers():
     assert all(run_ranks(_golden, 2))
 
 
-def _matches_torch(rank, world):
-    """Full outer step == reference math: per-tensor all_reduce(AVG) + SGD-Nesterov on snapshot."""
-    import torch.distributed as dist
-    env, m, dl = _mk(rank, seed=7)
-    st = m.store
-    g = torch.Generator().manual_seed(rank)
-    drift = 0.01 * torch.randn(st.numel, generator=g)
-    base = st.master.clone()
-    st.master.add_(drift)
-    # reference
-    p = torch.nn.Parameter(base.clone())
-    sgd = torch.optim.SGD([p], lr=0.7, momentum=0.9, nesterov=True)
-    grad = base - (base + drift)
-    dist.all_reduce(grad)
-    p.grad = grad / world
-    sgd.step()
-    dl.outer_step()
-    assert torch.allclose(st.master, p.detach(), atol=1e-6)
-    return True
+# shared with tests/test_transports_multiworker_gpu.py
+_matches_torch, _bf16_comm, _two_level = oc.dense_matches_torch, oc.dense_bf16_comm, oc.dense_two_level
 
 
 def test_outer_step_matches_torch_sgd_four_workers():
@@ -98,32 +82,8 @@ def test_overlapped_outer_step():
     assert all(run_ranks(_overlap, 2))
 
 
-def _bf16_comm(rank, world):
-    env, m, dl = _mk(rank, comm=torch.bfloat16, seed=9)
-    st = m.store
-    base = st.master.clone()
-    st.master.sub_(rank + 1.0)
-    dl.outer_step()
-    assert torch.allclose(st.master[: st.num_params], (base - 1.995)[: st.num_params], atol=2e-2)
-    assert dl.bytes_per_outer_step == st.numel * 2
-    return True
-
-
 def test_bf16_pseudograd_transport():
     assert all(run_ranks(_bf16_comm, 2))
-
-
-def _two_level(rank, world):
-    """4 ranks = 2 workers x 2-GPU inner DDP; sharded outer all-reduce + intra-worker all-gather."""
-    env, m, dl = _mk(rank, inner_dp=2, seed=11)
-    st = m.store
-    base = st.master.clone()
-    st.master.sub_(env.worker + 1.0)    # both GPUs of a worker drift identically
-    dl.outer_step()
-    assert torch.allclose(st.master[: st.num_params], (base - 1.995)[: st.num_params], atol=1e-5)
-    assert dl.bytes_per_outer_step == st.numel // 2 * 4
-    dl.check_replicas()
-    return True
 
 
 def test_two_level_sharded_outer():

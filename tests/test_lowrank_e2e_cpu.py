@@ -9,59 +9,16 @@ import numpy as np
 import pytest
 import torch
 
-from nanodiloco_amd.config import LlamaConfig
-from nanodiloco_amd.models import LlamaForCausalLM
-from nanodiloco_amd.optim import FlatAdamW, FlatOuterNesterov
-from nanodiloco_amd.parallel.diloco import Diloco
-from nanodiloco_amd.parallel.dist import init_distributed
-from nanodiloco_amd.parallel.transports import LowRankTransport
 
 from . import _lowrank_checks as chk
+from . import _outer_chains as oc
 from ._mp import child_env, free_port, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LR, MU = 0.7, 0.9
 SEQ = 64
 
 
-def _two_steps(rank, world, bucket_mb):
-    """Every worker drifts on its own; after each outer step theta_sync and the master are the same bits everywhere,
-    the residuals are each worker's own, and their mean is what the step did not deliver: with the first step's
-    momentum (buf = d) theta moved by lr (1 + mu) d, so mean_w(acc_w) - mean_w(e_w) = d must reproduce it."""
-    env = init_distributed("gloo")
-    m = LlamaForCausalLM(LlamaConfig(**chk.TINY)).init_weights(7)
-    dl = Diloco(m, FlatAdamW(m.store, lr=1e-3), FlatOuterNesterov(m.store, lr=LR, momentum=MU), 2, 8, 4, env=env,
-                comm_dtype=torch.float32, lowrank=4, bucket_mb=bucket_mb)
-    assert isinstance(dl.transport, LowRankTransport)
-    st, plan = m.store, dl.transport.plan
-    mask, comp = chk.covered(plan, st.numel)
-    tmask = torch.from_numpy(mask)
-    w1, w2 = dl.transport.wire1.numel(), dl.transport.wire2.numel()
-    assert dl.bytes_per_outer_step == 4 * (w1 + w2)
-    assert (dl.buckets_per_outer_step > 2) == (bucket_mb < 1)
-    for s in range(2):
-        drifts = [0.01 * torch.randn(st.numel, generator=torch.Generator().manual_seed(100 * s + j)) * tmask
-                  for j in range(world)]
-        theta = dl.sync.clone()
-        st.master.add_(drifts[env.worker])
-        dl.outer_step()
-        dl.check_replicas(tol=0.0)
-        assert torch.equal(st.master, dl.sync) and bool(torch.isfinite(st.master).all())
-        e = dl.lowrank_residual
-        assert bool(e[torch.from_numpy(comp)].any()) and not bool(e[~torch.from_numpy(comp)].any())
-        if s == 0:
-            es = [torch.zeros_like(e) for _ in range(world)]
-            torch.distributed.all_gather(es, e)
-            assert not torch.equal(es[0], es[1])
-            acc = torch.stack([-d for d in drifts]).double().mean(0)  # sync - master of worker j is -drift_j
-            d = acc - torch.stack(es).double().mean(0) * torch.from_numpy(comp)
-            moved = (theta - dl.sync).double()
-            # theta is rounded once where it is written (half an ulp of |theta|, taken as 2^-22 max|theta| with
-            # room for the two fma), d and the residuals carry fp32 roundings relative to the step itself
-            tol = 2.0 ** -22 * float(theta.abs().max()) + 1e-6 * float(moved.abs().max())
-            assert float((moved - LR * (1 + MU) * d).abs().max()) <= tol
-    assert dl.outer_comm.stats.calls == 2 * dl.buckets_per_outer_step
-    return True
+_two_steps = oc.lowrank_two_steps  # shared with tests/test_transports_multiworker_gpu.py
 
 
 @pytest.mark.parametrize("world", [2, 3])

@@ -13,7 +13,7 @@ from nanodiloco_amd.optim import FlatAdamW, FlatOuterNesterov
 from nanodiloco_amd.parallel.diloco import Diloco
 from nanodiloco_amd.parallel.dist import init_distributed
 
-from . import _qoracle as qo
+from . import _outer_chains as oc
 from ._mp import child_env, free_port, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,67 +54,8 @@ def test_golden_values_two_workers(comm):
     assert all(run_ranks(_golden, 2, comm))
 
 
-def _drift(n, rank):
-    return 0.01 * torch.randn(n, generator=torch.Generator().manual_seed(rank))
-
-
-def _oracle_step(base, deltas, bits):
-    """quantise each rank's delta, sum in rank order, requantise, dequantise -> (d_sum, sum of the ranks'
-    scales per element, the second scale per element), each of the span's length."""
-    n, w = base.numel(), len(deltas)
-    c = qo.chunk(n, w)
-    qs = [qo.quant_span(d, w, bits) for d in deltas]
-    out, s1, s2 = [], torch.zeros(w, c), torch.zeros(w, c)
-    for k in range(w):  # chunk k is reduced by worker k
-        codes = torch.stack([q[0][k] for q in qs])
-        scales = torch.stack([q[1][k] for q in qs])
-        rc, rs = qo.reduce_chunks(codes, scales, bits)
-        out.append(qo.dequant(rc, rs).view(-1))
-        s1[k] = scales.sum(dim=0).repeat_interleave(qo.QB)
-        s2[k] = rs.view(-1).repeat_interleave(qo.QB)
-    return torch.cat(out)[:n], s1.view(-1)[:n], s2.view(-1)[:n]
-
-
-def _random_drift(rank, world, comm, inner_dp):
-    bits = int(comm[3:])
-    env, m, dl = _mk(comm, inner_dp=inner_dp)
-    st = m.store
-    base = st.master.clone()
-    w = env.num_workers
-    a, b = dl.my_shard
-    # every GPU of a worker drifts identically; each rank can rebuild every worker's drift
-    drifts = [_drift(st.numel, k) for k in range(w)]
-    st.master.add_(drifts[env.worker])
-    # in-test oracle, shard by shard (the two-level mode reduces shard i on the i-th GPU of every worker)
-    want = base.clone()
-    bound = torch.zeros_like(base)
-    for x, y in dl.shards:
-        deltas = [base[x:y] - (base[x:y] + d[x:y]) for d in drifts]
-        dsum, s1, s2 = _oracle_step(base[x:y], deltas, bits)
-        p = torch.nn.Parameter(base[x:y].clone())
-        sgd = torch.optim.SGD([p], lr=LR, momentum=MU, nesterov=True)
-        p.grad = dsum * (1.0 / w)
-        sgd.step()
-        want[x:y] = p.detach()
-        bound[x:y] = (s1 / 2 + s2 / 2) / w * LR * (1 + MU)
-    dl.outer_step()
-    diff = (st.master - want).abs().max().item()
-    print(f"{comm} W={w} inner_dp={inner_dp}: max |master - oracle| = {diff:.3e}")
-    assert torch.equal(st.master, want), diff
-    assert torch.equal(dl.sync, st.master)
-    dl.check_replicas(tol=0.0)
-    c = qo.chunk(b - a, w)
-    assert dl.bytes_per_outer_step == w * (c * bits // 8 + c // 256 * 4)
-    assert dl.buckets_per_outer_step == 1
-    # against fp32 transport: the same step on a second instance
-    _, m2, dl2 = _mk(torch.float32, env=env)
-    assert torch.equal(m2.store.master, base)
-    m2.store.master.add_(drifts[env.worker])
-    dl2.outer_step()
-    err = (st.master - m2.store.master).abs()
-    print(f"{comm}: max |quantised - fp32| = {err.max().item():.3e}, smallest bound {bound[bound > 0].min().item():.3e}")
-    assert bool((err <= bound)[: st.num_params].all()), (err - bound).max()
-    return True
+# shared with tests/test_transports_multiworker_gpu.py
+_random_drift, _several_buckets = oc.q_random_drift, oc.q_several_buckets
 
 
 @pytest.mark.parametrize("comm", COMM)
@@ -125,29 +66,6 @@ def test_random_drift_four_workers_matches_oracle_bitwise(comm):
 @pytest.mark.parametrize("comm", COMM)
 def test_two_level_quantised(comm):
     assert all(run_ranks(_random_drift, 4, comm, 2))
-
-
-def _several_buckets(rank, world):
-    """Three workers, a bucket size that cuts the span into many buckets with a padded last one, the
-    host-offloaded snapshot: identical to the one-bucket plan's oracle only per bucket, so check the
-    invariants -- replicas bit-identical, bytes, and agreement with fp32 transport within the format's bound
-    (one scale per block bounds both roundings by amax / QMAX each)."""
-    env, m, dl = _mk("int8", bucket_mb=3 * 256 / (1 << 20), offload_snapshot=True)
-    st = m.store
-    base = st.master.clone()
-    st.master.add_(_drift(st.numel, rank))
-    assert dl.buckets_per_outer_step == -(-st.numel // (3 * 256)) and dl.buckets_per_outer_step > 3
-    assert dl.bytes_per_outer_step == dl.buckets_per_outer_step * 3 * 260
-    dl.outer_step(phases=True)
-    dl.check_replicas(tol=0.0)
-    assert torch.equal(dl.sync, st.master) and dl.sync.device.type == "cpu"
-    _, m2, dl2 = _mk(torch.float32, env=env)
-    m2.store.master.add_(_drift(st.numel, rank))
-    dl2.outer_step()
-    amax = 0.01 * 6  # |drift| < 6 sigma
-    assert (st.master - m2.store.master).abs().max().item() <= (3 * amax / 127 / 2 + 3 * amax / 127 / 2) / 3 * LR * (1 + MU)
-    assert dl.outer_comm.stats.calls == 2 * dl.buckets_per_outer_step
-    return True
 
 
 def test_three_workers_many_buckets_offloaded_snapshot():

@@ -14,10 +14,8 @@ from nanodiloco_amd.models import LlamaForCausalLM
 from nanodiloco_amd.optim import FlatAdamW, FlatOuterNesterov
 from nanodiloco_amd.parallel.diloco import Diloco
 from nanodiloco_amd.parallel.dist import init_distributed
-from nanodiloco_amd.utils.checkpoint import load_checkpoint, save_checkpoint
 
-from . import _qef_checks as chk
-from . import _qoracle as qo
+from . import _outer_chains as oc
 from ._mp import child_env, free_port, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,8 +23,6 @@ TINY = dict(hidden_size=32, intermediate_size=64, num_attention_heads=2, num_hid
             rms_norm_eps=1e-5)
 LR, MU = 0.7, 0.9
 COMM = ["int8", "int4"]
-STEPS = 3
-SIGMA = 0.01
 
 
 def _mk(comm, inner_dp=1, seed=7, env=None, ef=True, **kw):
@@ -37,63 +33,9 @@ def _mk(comm, inner_dp=1, seed=7, env=None, ef=True, **kw):
     return env, m, dl
 
 
-def _drift(n, step, worker):
-    return SIGMA * torch.randn(n, generator=torch.Generator().manual_seed(100 * step + worker))
-
-
 # ------------------------------------------------------------------------------------- 6. bitwise chain
-def _chain(rank, world, comm, inner_dp):
-    """Three outer steps, a fresh drift per step and worker; the master must equal an in-test chain that carries
-    e1 per worker and e2 per chunk through the oracle of tests/_qef_checks.py and feeds torch.optim.SGD."""
-    bits = int(comm[3:])
-    env, m, dl = _mk(comm, inner_dp=inner_dp)
-    st = m.store
-    w = env.num_workers
-    _, m0, dl0 = _mk(comm, env=env, ef=False)  # the stateless transport, for step 1
-    shards = dl.shards
-    theta = st.master.clone()  # the oracle's theta_sync
-    ps, sgds, e1, e2 = [], [], [], []
-    for x, y in shards:
-        p = torch.nn.Parameter(theta[x:y].clone())
-        ps.append(p)
-        sgds.append(torch.optim.SGD([p], lr=LR, momentum=MU, nesterov=True))
-        c = qo.chunk(y - x, w)
-        e1.append([torch.zeros(y - x) for _ in range(w)])
-        e2.append([torch.zeros(c) for _ in range(w)])
-    for s in range(STEPS):
-        drifts = [_drift(st.numel, s, k) for k in range(w)]  # every GPU of a worker drifts identically
-        st.master.add_(drifts[env.worker])
-        for i, (x, y) in enumerate(shards):
-            stage1 = []
-            for k in range(w):
-                oc, os_, e1[i][k] = chk.oracle_stage1(theta[x:y], theta[x:y] + drifts[k][x:y], e1[i][k], w, bits)
-                stage1.append((oc, os_))
-            out = []
-            for k in range(w):  # chunk k is reduced by worker k, which keeps e2 for it
-                codes = torch.stack([q[0][k] for q in stage1])
-                scales = torch.stack([q[1][k] for q in stage1])
-                rc, rs, e2[i][k] = chk.oracle_stage2(codes, scales, e2[i][k], bits)
-                out.append(qo.dequant(rc, rs).view(-1))
-            ps[i].grad = torch.cat(out)[: y - x] * (1.0 / w)
-            sgds[i].step()
-            theta[x:y] = ps[i].detach()
-        dl.outer_step()
-        diff = (st.master - theta).abs().max().item()
-        print(f"{comm} W={w} inner_dp={inner_dp} step {s + 1}: max |master - oracle| = {diff:.3e}")
-        assert torch.equal(st.master, theta), (s, diff)
-        assert torch.equal(dl.sync, st.master)
-        dl.check_replicas(tol=0.0)
-        a, b = dl.my_shard
-        i = shards.index((a, b))
-        assert chk.same_bits(dl.qef_send, e1[i][env.worker])
-        assert chk.same_bits(dl.qef_reduce, e2[i][env.worker])
-        if s == 0:
-            m0.store.master.add_(drifts[env.worker])
-            dl0.outer_step()
-            assert torch.equal(m0.store.master, st.master), "step 1 (zero residuals) must equal the stateless step"
-            assert dl.bytes_per_outer_step == dl0.bytes_per_outer_step
-            assert dl.buckets_per_outer_step == dl0.buckets_per_outer_step == 1
-    return bool((dl.qef_send != 0).any())
+# the chains are shared with tests/test_transports_multiworker_gpu.py
+_chain, _several_buckets, _checkpoints = oc.qef_chain, oc.qef_several_buckets, oc.qef_checkpoints
 
 
 @pytest.mark.parametrize("comm", COMM)
@@ -108,114 +50,11 @@ def test_two_level_error_feedback(comm):
 
 
 # ------------------------------------------------------------------------------------- 7. many buckets
-def _several_buckets(rank, world):
-    """Three workers, buckets of 4 x 3 x 256 elements and a shorter last one (the flat size is a multiple of
-    64 * 840, hence of 3 x 256: with three workers a last bucket is shorter, never padded -- padded chunks are the
-    op-level sizes of tests/_qef_checks.py), the host-offloaded snapshot.  Against an fp32-transport run of the
-    same drifts the difference after T steps is bounded by the delivered-sum bound (tests/_qef_checks.py:
-    sum_w s1_w / 2 + s2 / 2 + slack, the sum of the residuals) times lr (1 + mu) / W, with the scales bounded as in
-    tests/test_qcomm_e2e_cpu.py: |drift| < 6 sigma, so s1 <= amax / 127 for each of the three workers and
-    s2 <= 3 amax / 127."""
-    unit = 3 * 256
-    env, m, dl = _mk("int8", bucket_mb=4 * unit / (1 << 20), offload_snapshot=True)
-    st = m.store
-    a, b = dl.my_shard
-    nb = -(-st.numel // (4 * unit))
-    last = st.numel - (nb - 1) * 4 * unit
-    assert dl.buckets_per_outer_step == nb > 3 and 0 < last < 4 * unit
-    assert [bk.c for bk in dl.transport._qplan] == [4 * 256] * (nb - 1) + [last // 3]
-    assert dl.bytes_per_outer_step == sum(3 * (bk.c + bk.c // 256 * 4) for bk in dl.transport._qplan)
-    assert dl.qef_send.numel() == b - a == st.numel
-    assert dl.qef_reduce.numel() == sum(bk.c for bk in dl.transport._qplan) == (nb - 1) * 4 * 256 + last // 3
-    assert [v.numel() for v in dl.transport._qef_views] == [bk.c for bk in dl.transport._qplan]
-    assert all(v.data_ptr() == dl.qef_reduce.data_ptr() + 4 * 4 * 256 * i
-               for i, v in enumerate(dl.transport._qef_views))
-    _, m2, dl2 = _mk(torch.float32, env=env, ef=False)
-    amax = SIGMA * 6
-    resid = 3 * amax / 127 / 2 + 3 * amax / 127 / 2 + STEPS * (3 + 1) * 2.0 ** -23 * (2 * 3 * amax)
-    bound = resid * LR * (1 + MU) / 3
-    for s in range(STEPS):
-        for mm, dd in ((m, dl), (m2, dl2)):
-            mm.store.master.add_(_drift(st.numel, s, rank))
-            dd.outer_step()
-        dl.check_replicas(tol=0.0)
-        assert torch.equal(dl.sync, st.master) and dl.sync.device.type == "cpu"
-        err = (st.master - m2.store.master).abs().max().item()
-        print(f"step {s + 1}: max |error feedback - fp32 transport| = {err:.3e}, bound {bound:.3e}")
-        assert err <= bound
-    assert dl.outer_comm.stats.calls == STEPS * 2 * nb
-    return True
-
-
 def test_three_workers_many_buckets_offloaded_snapshot():
     assert all(run_ranks(_several_buckets, 3))
 
 
 # ------------------------------------------------------------------------------------- 8. checkpoint
-BUCKET = 2048 / (1 << 20)  # 2048 (int8) / 4096 (int4) elements per bucket: the two plans differ
-
-
-def _step(m, dl, s):
-    """one outer step after a drift of the parameters alone: a checkpoint stores the model by parameter, so the
-    alignment padding of the flat vector (which training never moves) comes back as it was initialised"""
-    st = m.store
-    real = torch.zeros(st.numel, dtype=torch.bool)
-    for name in st.names:
-        real[st.offsets[name]:st.offsets[name] + st.master_view(name).numel()] = True
-    st.master.add_(_drift(st.numel, s, dl.env.worker) * real)
-    dl.outer_step()
-
-
-def _checkpoints(rank, world, tmp):
-    env, m, dl = _mk("int8", bucket_mb=BUCKET)
-    assert len(dl.transport._qplan) > 2
-    _step(m, dl, 0)
-    save_checkpoint(os.path.join(tmp, "ef"), m, dl, env, 4)
-    send1, red1 = dl.qef_send.clone(), dl.qef_reduce.clone()
-    assert bool((send1 != 0).any()) and bool((red1 != 0).any())
-    _step(m, dl, 1)
-    with open(os.path.join(tmp, "ef", "trainer_state.json")) as f:
-        meta = json.load(f)["comm_error_feedback"]
-    assert meta == {"bits": 8, "num_workers": 2, "plan": [[bk.x, bk.y, bk.c] for bk in dl.transport._qplan]}
-    # save after step 1, load into a fresh instance, step 2: the uninterrupted run, bitwise
-    _, m2, dl2 = _mk("int8", env=env, bucket_mb=BUCKET, seed=8)
-    load_checkpoint(os.path.join(tmp, "ef"), m2, dl2, env)
-    assert torch.equal(dl2.qef_send, send1) and torch.equal(dl2.qef_reduce, red1)
-    _step(m2, dl2, 1)
-    assert torch.equal(m2.store.master, m.store.master) and torch.equal(dl2.sync, dl.sync)
-    assert torch.equal(dl2.qef_send, dl.qef_send) and torch.equal(dl2.qef_reduce, dl.qef_reduce)
-    # a stateless checkpoint, resumed with the flag on: zero residuals, the run goes on
-    _, m3, dl3 = _mk("int8", env=env, bucket_mb=BUCKET, ef=False)
-    _step(m3, dl3, 0)
-    save_checkpoint(os.path.join(tmp, "plain"), m3, dl3, env, 4)
-    with open(os.path.join(tmp, "plain", "trainer_state.json")) as f:
-        assert "comm_error_feedback" not in json.load(f)
-    _, m4, dl4 = _mk("int8", env=env, bucket_mb=BUCKET, seed=9)
-    dl4.qef_send.fill_(1.0)  # whatever was there is dropped
-    dl4.qef_reduce.fill_(1.0)
-    load_checkpoint(os.path.join(tmp, "plain"), m4, dl4, env)
-    assert not bool(dl4.qef_send.any()) and not bool(dl4.qef_reduce.any())
-    _step(m4, dl4, 1)
-    dl4.check_replicas(tol=0.0)
-    assert bool(torch.isfinite(m4.store.master).all()) and bool((dl4.qef_send != 0).any())
-    # a checkpoint with residuals, resumed without the flag: ignored, the stateless run of that state
-    _, m5, dl5 = _mk("int8", env=env, bucket_mb=BUCKET, ef=False, seed=10)
-    load_checkpoint(os.path.join(tmp, "ef"), m5, dl5, env)
-    assert dl5.error_feedback_state() is None and not hasattr(dl5, "qef_send")
-    _step(m5, dl5, 1)
-    dl5.check_replicas(tol=0.0)
-    assert bool(torch.isfinite(m5.store.master).all()) and not torch.equal(m5.store.master, m.store.master)
-    # int8 -> int4: qef.send is per element and stays; qef.reduce follows the plan, which differs: zero
-    _, m6, dl6 = _mk("int4", env=env, bucket_mb=BUCKET, seed=11)
-    assert [[bk.x, bk.y, bk.c] for bk in dl6.transport._qplan] != meta["plan"]
-    dl6.qef_reduce.fill_(1.0)
-    load_checkpoint(os.path.join(tmp, "ef"), m6, dl6, env)
-    assert torch.equal(dl6.qef_send, send1) and not bool(dl6.qef_reduce.any())
-    _step(m6, dl6, 1)
-    dl6.check_replicas(tol=0.0)
-    return True
-
-
 def test_checkpoint_roundtrip_and_resume_rules(tmp_path):
     assert all(run_ranks(_checkpoints, 2, str(tmp_path)))
 

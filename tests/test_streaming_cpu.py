@@ -16,6 +16,7 @@ from nanodiloco_amd.parallel.diloco import Diloco
 from nanodiloco_amd.parallel.dist import init_distributed
 from nanodiloco_amd.parallel.fragments import fragment_due, plan_fragments
 
+from . import _outer_chains as oc
 from ._mp import child_env, free_port, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,10 +37,6 @@ def _diloco(m, env=None, **kw):
 def _no_group():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         os.environ.pop(k, None)
-
-
-def _cat(t, spans):
-    return torch.cat([t[a:b] for a, b in spans])
 
 
 # ------------------------------------------------------------------ 1. plan
@@ -178,35 +175,7 @@ def test_one_fragment_is_bitwise_the_classic_outer_step():
 
 
 # ------------------------------------------------------------------ 4. per-fragment golden values
-def _golden(rank, world):
-    env = init_distributed("gloo")
-    m = _model(100 + rank)  # the init broadcast makes the replicas identical
-    dl = _diloco(m, env=env, fragments=2)
-    st = m.store
-    f0, f1 = (t.spans for t in dl.frag_tables)
-    theta0 = st.master.clone()
-    st.master.sub_(rank + 1.0)  # delta = r + 1, average 1.5
-    local = st.master.clone()
-    assert dl.stream_step(H // 2) == {"sent": 0, "applied": 0}
-    step1 = _cat(st.master - theta0, f0)
-    assert torch.allclose(step1, torch.full_like(step1, -1.995), atol=1e-5), step1[:4]
-    assert torch.equal(_cat(st.master, f1), _cat(local, f1))            # fragment 1: bitwise untouched
-    assert torch.equal(_cat(dl.sync, f1), _cat(theta0, f1))
-    assert not dl.outer_optimizer.momentum_buffer[f1[0][0]:f1[0][1]].any()
-    assert torch.equal(_cat(dl.sync, f0), _cat(st.master, f0))
-    # second sync of fragment 0 with zero drift: its own momentum only (fragment 1 never synced in between)
-    th1 = st.master.clone()
-    assert dl.stream_step(H + H // 2) == {"sent": 0, "applied": 0}
-    step2 = _cat(st.master - th1, f0)
-    assert torch.allclose(step2, torch.full_like(step2, -0.8505), atol=1e-5), step2[:4]
-    assert torch.equal(_cat(st.master, f1), _cat(local, f1))
-    assert dl.frag_steps == [2, 0] and dl.outer_step_count == 0
-    # fragment 1's first sync still takes the `first` branch with its own (zero) history
-    assert dl.stream_step(2 * H) == {"sent": 1, "applied": 1}
-    step3 = _cat(st.master - theta0, f1)
-    assert torch.allclose(step3, torch.full_like(step3, -1.995), atol=1e-5)
-    assert dl.frag_steps == [2, 1] and dl.outer_step_count == 1
-    return True
+_golden = oc.stream_golden  # shared with tests/test_transports_multiworker_gpu.py
 
 
 def test_golden_values_per_fragment():
@@ -214,38 +183,7 @@ def test_golden_values_per_fragment():
 
 
 # ------------------------------------------------------------------ 5. tau and alpha
-def _tau_alpha(rank, world, alpha):
-    import torch.distributed as dist
-    env = init_distributed("gloo")
-    m = _model(5)
-    dl = _diloco(m, env=env, fragments=2, stream_overlap=1, stream_alpha=alpha)
-    st = m.store
-    f0, f1 = (t.spans for t in dl.frag_tables)
-    theta0 = st.master.clone()
-    st.master.sub_(rank + 1.0)
-    assert dl.stream_step(H // 2) == {"sent": 0, "applied": None}
-    assert torch.equal(st.master, theta0 - (rank + 1.0))                 # nothing applied yet
-    st.master.add_(0.25)                                                 # local progress inside the window
-    local_now = st.master.clone()
-    assert dl.stream_step(H // 2 + 1) == {"sent": None, "applied": 0}
-    theta_new = _cat(theta0, f0) - 1.995
-    assert torch.allclose(_cat(dl.sync, f0), theta_new, atol=1e-5)
-    if alpha:
-        expect = alpha * _cat(local_now, f0) + (1 - alpha) * _cat(dl.sync, f0)
-        assert torch.allclose(_cat(st.master, f0), expect, atol=1e-5)
-        assert not torch.equal(_cat(st.master, f0), _cat(dl.sync, f0))
-    else:  # the local progress on the fragment is discarded
-        assert torch.equal(_cat(st.master, f0), _cat(dl.sync, f0))
-    gathered = [torch.zeros_like(dl.sync) for _ in range(world)]
-    dist.all_gather(gathered, dl.sync)
-    assert all(torch.equal(g, gathered[0]) for g in gathered)            # theta_new identical on every rank
-    assert torch.equal(_cat(st.master, f1), _cat(local_now, f1))         # the other fragment: unchanged
-    assert torch.equal(_cat(dl.sync, f1), _cat(theta0, f1))
-    dl.check_replicas()  # local weights legitimately differ; theta_sync must not
-    dl.flush_fragments()
-    assert torch.equal(st.master, dl.sync)
-    dl.check_replicas()
-    return True
+_tau_alpha = oc.stream_tau_alpha  # shared with tests/test_transports_multiworker_gpu.py
 
 
 @pytest.mark.parametrize("alpha", [0.5, 0.0])

@@ -5,7 +5,6 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 
@@ -18,8 +17,8 @@ from nanodiloco_amd.parallel.diloco import Diloco, _check_options
 from nanodiloco_amd.parallel.dist import init_distributed
 from nanodiloco_amd.parallel.transports import DenseTransport, TopKTransport
 
+from . import _outer_chains as oc
 from . import _topk_checks as chk
-from . import _topk_oracle as to
 from ._mp import child_env, free_port, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,45 +46,7 @@ def _no_dist_env():
 
 
 # ------------------------------------------------------------------------------------- 1. the oracle's steps
-def _chain(rank, world, comm, k, inner_dp, bucket_mb):
-    """Two outer steps, a fresh drift per step and worker.  The oracle selects for every worker and shard, carries
-    each residual, sums the slots in worker order and feeds ``ops.outer_nesterov``; master, sync, momentum and this
-    rank's residual must equal it bit for bit."""
-    bf16 = comm == torch.bfloat16
-    env, m, dl = _mk(comm, k, inner_dp=inner_dp, bucket_mb=bucket_mb)
-    assert isinstance(dl.transport, TopKTransport)
-    st = m.store
-    w = env.num_workers
-    shards = dl.shards
-    theta, mom = st.master.clone(), torch.zeros_like(st.master)
-    e = [[np.zeros(y - x, dtype=np.float32) for _ in range(w)] for x, y in shards]
-    a, b = dl.my_shard
-    mine = shards.index((a, b))
-    assert dl.bytes_per_outer_step == sum(ops.topk_slot_bytes(bk.y - bk.x, k, comm) for bk in dl.transport._plan)
-    assert all(bk.x % to.CHUNK == 0 for bk in dl.transport._plan)
-    if bucket_mb >= 1:
-        assert dl.buckets_per_outer_step == 1 and dl.bytes_per_outer_step == ops.topk_slot_bytes(b - a, k, comm)
-    else:
-        assert dl.buckets_per_outer_step > 1
-    for s in range(2):
-        drifts = [_drift(st.numel, s, j) for j in range(w)]  # every GPU of a worker drifts identically
-        st.master.add_(drifts[env.worker])
-        for i, (x, y) in enumerate(shards):
-            slots = []
-            for j in range(w):
-                local = (theta + drifts[j])[x:y].numpy()
-                idx, val, e[i][j], _ = to.select(theta[x:y].numpy(), local, e[i][j], k, bf16)
-                slots.append((idx, val))
-            dsum = torch.from_numpy(to.dense_sum(slots, y - x))
-            ops.outer_nesterov(theta[x:y].clone(), theta[x:y], dsum, mom[x:y], None, 1.0 / w, LR, MU, s == 0)
-        dl.outer_step()
-        assert torch.equal(st.master, theta), (s, (st.master - theta).abs().max().item())
-        assert torch.equal(dl.sync, theta)
-        assert torch.equal(dl.outer_optimizer.momentum_buffer[a:b], mom[a:b])
-        assert chk.same_bits(dl.topk_residual, e[mine][env.worker])
-        dl.check_replicas(tol=0.0)
-    assert dl.outer_comm.stats.calls == 2 * dl.buckets_per_outer_step
-    return bool((dl.topk_residual != 0).any())
+_chain = oc.topk_chain  # shared with tests/test_transports_multiworker_gpu.py
 
 
 @pytest.mark.parametrize("comm", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
