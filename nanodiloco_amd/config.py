@@ -96,6 +96,7 @@ class LlamaConfig:
     attention_bias: bool = False
     attention_dropout: float = 0.0
     mlp_bias: bool = False
+    qk_norm: bool = False  # per-head RMSNorm of q and k before RoPE (Qwen3), docs/DESIGN.md "QK-norm"
     architectures: Optional[list] = None
     extra: Dict[str, Any] = dataclasses.field(default_factory=dict)
 
@@ -118,6 +119,8 @@ class LlamaConfig:
         known = {f.name for f in dataclasses.fields(cls)} - {"extra"}
         kw = {k: v for k, v in d.items() if k in known}
         extra = {k: v for k, v in d.items() if k not in known}
+        if d.get("model_type") == "qwen3" or d.get("architectures") == ["Qwen3ForCausalLM"]:
+            kw["qk_norm"] = True  # HF Qwen3 has no such key: the architecture implies it
         return cls(**kw, extra=extra)
 
     @classmethod
@@ -129,6 +132,8 @@ class LlamaConfig:
         extra = d.pop("extra")
         d.update(extra)
         d.pop("rope_parameters", None)
+        if not self.qk_norm:
+            del d["qk_norm"]  # off: the dict is what it always was
         if d.get("architectures") is None:
             d["architectures"] = ["LlamaForCausalLM"]
         return d
@@ -137,6 +142,8 @@ class LlamaConfig:
         """config.json content loadable by ``transformers.LlamaForCausalLM.from_pretrained``."""
         d = self.to_dict()
         d["model_type"] = "llama"
+        if self.qk_norm:  # Llama + QK-norm is HF Qwen3: same tensor names, same math (head_dim is explicit there)
+            d["model_type"], d["architectures"], d["head_dim"] = "qwen3", ["Qwen3ForCausalLM"], self.head_dim
         d["torch_dtype"] = "float32"
         return d
 
@@ -171,6 +178,11 @@ class LlamaConfig:
                 (p + "self_attn.k_proj.weight", (self.kv_size, d)),
                 (p + "self_attn.v_proj.weight", (self.kv_size, d)),
                 (p + "self_attn.o_proj.weight", (d, self.q_size)),
+            ]
+            if self.qk_norm:  # HF Qwen3's state-dict order; q|k|v stay adjacent for the fused views
+                out += [(p + "self_attn.q_norm.weight", (self.head_dim,)),
+                        (p + "self_attn.k_norm.weight", (self.head_dim,))]
+            out += [
                 (p + "mlp.gate_proj.weight", (f, d)),
                 (p + "mlp.up_proj.weight", (f, d)),
                 (p + "mlp.down_proj.weight", (d, f)),

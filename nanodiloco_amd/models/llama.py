@@ -8,6 +8,8 @@ weights load here.  The compute graph is our own:
   y   = rmsnorm(h0) * w_in[0]               compute dtype (bf16)
   per layer:
     qkv = rope(y @ [Wq|Wk|Wv]^T)            ONE GEMM (fused view of the flat buffer), RoPE in its epilogue
+                                            (config.qk_norm: the plain GEMM, then a per-head RMSNorm of q and k fused
+                                            with RoPE in one pass over q|k, ops.qk_norm_rope)
     o   = flash_attn(qkv)                   HIP kernel, reads packed qkv, writes [N, nh*hd]
     y,h = add_rmsnorm(h, o @ Wo^T, w_post)  residual add fused into the norm
     act = swiglu(y @ [Wgate|Wup]^T)         ONE GEMM, SwiGLU in its epilogue (SwiGLU backward in the
@@ -165,6 +167,15 @@ class LlamaForCausalLM:
         c, proj = self.config, self.proj
         p = f"model.layers.{i}."
         qkv, rotated = proj.qkv(i, y, y8, cos, sin, T)  # rotated: RoPE ran in the GEMM epilogue
+        if c.qk_norm:
+            # the plain projection (never the RoPE epilogue), then norm + RoPE in one pass over q|k (HIP) or the norm
+            # alone (PyTorch path); the attention backward hands back the gradient of the normed, un-rotated q|k
+            qkv, rotated = ops.qk_norm_rope(qkv, self._m(p + "self_attn.q_norm.weight"),
+                                            self._m(p + "self_attn.k_norm.weight"),
+                                            self._g(p + "self_attn.q_norm.weight"),
+                                            self._g(p + "self_attn.k_norm.weight"), cos, sin, T,
+                                            c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps,
+                                            inplace=True)
         o = ops.attention(qkv, cos, sin, B, T, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
                           inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc)
         if cache is not None:
@@ -319,6 +330,9 @@ class LlamaForCausalLM:
         for i in range(L):
             p = f"model.layers.{i}."
             qkv = ops.mm_nt(y, self._fused(self._qkv_names[i], "shadow"))
+            if c.qk_norm:  # in place on the new row; the decode kernel rotates what it finds there
+                ops.qk_norm(qkv, self._m(p + "self_attn.q_norm.weight"), self._m(p + "self_attn.k_norm.weight"),
+                            c.num_attention_heads, c.num_key_value_heads, c.head_dim, eps)
             o = ops.attention_decode(qkv, cache, i, cos, sin)
             a = ops.mm_nt(o, self._w(p + "self_attn.o_proj.weight"))
             y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"), None, eps, cdt)

@@ -73,7 +73,8 @@ class Bf16Projections:
     def qkv(self, i, y, y8, cos, sin, T):  # -> (projection, whether RoPE ran in the GEMM epilogue)
         w, gw, hd, rope_cols = self.qkv_w(i)
         wt = self._wt(f"{i}.qkv", w)
-        if linear_rope_supported(y, w, wt, hd, rope_cols):
+        # QK-norm sits between the projection and RoPE: the plain GEMM, and ops.qk_norm_rope rotates
+        if not self.m().config.qk_norm and linear_rope_supported(y, w, wt, hd, rope_cols):
             # own GEMM with RoPE on q|k in its epilogue: the attention skips its rotation pass
             return linear_rope(y, w, gw, wt, cos, sin, T, hd, rope_cols), True
         return linear(y, w, gw, wt), False
@@ -141,13 +142,13 @@ class Fp8Projections:
     def qkv(self, i, y, y8, cos, sin, T):
         if not fp8.fp8_projection("qkv"):
             out = self.bf16.qkv(i, y, y8, cos, sin, T)
-            if not out[1]:
+            if not out[1] and not self.m().config.qk_norm:  # with QK-norm the plain GEMM is the intended one
                 self._warn_once("qkv", "--fp8-keep-fused rope: the fused bf16 q|k|v + RoPE GEMM cannot run on this "
                                        "shape; the projection runs as a plain bf16 GEMM + separate RoPE pass (slower "
                                        "than fp8)")
             return out
         w, gw, hd, rope_cols = self.bf16.qkv_w(i)
-        if self.lin.rope_ok(y, w, hd, rope_cols):
+        if not self.m().config.qk_norm and self.lin.rope_ok(y, w, hd, rope_cols):
             # e4m3 operands on the own fp8 GEMM, RoPE on the dequantised accumulator
             return self.lin(f"{i}.qkv", y, w, gw, self.m().store.version, y8, (cos, sin, T, hd, rope_cols)), True
         return self.lin(f"{i}.qkv", y, w, gw, self.m().store.version, y8), False

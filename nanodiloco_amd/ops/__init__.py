@@ -6,6 +6,7 @@ from .linear import linear, wgrad_accumulate, set_wgrad_overlap, wgrad_overlap_e
     set_fused_epilogues, fused_epilogues, linear_rope, linear_rope_supported, mlp_fused, mlp_fused_supported, \
     set_wgrad_group, wgrad_group_enabled
 from .norm import rmsnorm, rmsnorm_res, add_rmsnorm
+from .qk_norm import qk_norm, qk_norm_rope
 from .embedding import embedding
 from .swiglu import swiglu
 from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding, doc_bounds, \
@@ -26,7 +27,7 @@ from . import reference
 __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "linear", "wgrad_accumulate",
            "set_wgrad_overlap", "wgrad_overlap_enabled", "join_wgrad", "set_wgrad_group", "wgrad_group_enabled",
            "set_dgrad_transposed", "dgrad_transposed_enabled", "transpose_into",
-           "rmsnorm", "rmsnorm_res", "add_rmsnorm", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
+           "rmsnorm", "rmsnorm_res", "add_rmsnorm", "qk_norm", "qk_norm_rope", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
            "KVCache", "attention_decode", "cache_fill", "decode_split",
            "lm_head_ce", "lm_head_ce_parts", "LMHeadLoss", "lm_head_loss",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",

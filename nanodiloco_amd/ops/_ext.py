@@ -142,6 +142,10 @@ def _declare(L: ctypes.CDLL):
         "nd_transpose_bf16": [P, P, I, I, L64, L64, P],
         # rope (in place on packed qkv)
         "nd_rope_inplace": [P, I, P, P, L64, I, I, I, I, I, I, P],
+        # QK-norm on the q|k heads of packed qkv (csrc/qk_norm.hip): alone, fused with RoPE (+ rstd, raw q|k), backward
+        "nd_qk_norm": [P, I, P, P, L64, I, I, I, L64, F, P],
+        "nd_qk_norm_rope_fwd": [P, I, P, P, P, P, P, P, L64, I, I, I, I, L64, F, P],
+        "nd_qk_norm_bwd": [P, I, P, P, P, P, P, I, P, P, L64, I, I, I, L64, P],
         # attention
         "nd_attn_fwd": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P],
         "nd_attn_fwd_ks": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P, P],

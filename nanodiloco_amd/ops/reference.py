@@ -48,6 +48,32 @@ def rmsnorm_backward(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, eps: fl
     return dx, dw
 
 
+def qk_norm(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, nh: int, nkv: int, hd: int,
+            eps: float) -> torch.Tensor:
+    """QK-norm: RMSNorm over ``hd`` of every q and k head of packed rows [N, (nh + 2 nkv) * hd] (fp32 statistics,
+    ``w * (x * rstd)`` rounded once to the input dtype, as ``rmsnorm``); the v columns pass through.  Out of place,
+    autograd-capable."""
+    N = qkv.shape[0]
+    q, k, v = qkv.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
+    q = rmsnorm(q.reshape(N, nh, hd), wq, eps).reshape(N, nh * hd)
+    k = rmsnorm(k.reshape(N, nkv, hd), wk, eps).reshape(N, nkv * hd)
+    return torch.cat([q, k, v], dim=-1)
+
+
+def qk_norm_backward(dy: torch.Tensor, qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, nh: int, nkv: int,
+                     hd: int, eps: float):
+    """(dx in the dtype of ``qkv``, dwq fp32, dwk fp32) of ``qk_norm`` for the gradient ``dy`` of its output; the v
+    columns of ``dy`` pass through."""
+    N = qkv.shape[0]
+    x = qkv.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
+    d = dy.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
+    dq, dwq = rmsnorm_backward(d[0].reshape(N, nh, hd), x[0].reshape(N, nh, hd), wq, eps)
+    dk, dwk = rmsnorm_backward(d[1].reshape(N, nkv, hd), x[1].reshape(N, nkv, hd), wk, eps)
+    dx = torch.cat([dq.reshape(N, nh * hd).to(qkv.dtype), dk.reshape(N, nkv * hd).to(qkv.dtype),
+                    d[2].to(qkv.dtype)], dim=-1)
+    return dx, dwq, dwk
+
+
 # ----------------------------------------------------------------------------- rope
 def rope_inv_freq(head_dim: int, theta: float, scaling: Optional[dict] = None, device=None) -> torch.Tensor:
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64, device=device).float() / head_dim))

@@ -64,6 +64,9 @@ class TrainArgs:
     z_loss: float = 0.0            # z-loss coefficient: the objective gains z_loss * mean(logsumexp(logits)^2) inside
                                    # the lm-head CE kernels (docs/DESIGN.md "z-loss"); 0 = off.  The logged `loss`
                                    # stays the cross-entropy, the weighted term is logged as `z_loss`
+    qk_norm: bool = False          # QK-norm: a per-head RMSNorm of q and k before RoPE with one learnable [head_dim]
+                                   # weight each per layer (Qwen3; docs/DESIGN.md "QK-norm").  Forces the model
+                                   # config's `qk_norm` key on; a resumed checkpoint's config.json turns it on as well
     inner_optimizer: str = "adamw"  # adamw | muon: Muon ("MuLoCo") on the decoder projection weights, AdamW on the
                                     # rest (optim.FlatMuon, docs/DESIGN.md "Muon inner optimizer")
     muon_momentum: float = 0.95
@@ -196,6 +199,22 @@ def check_doc_mask(doc_mask: bool, data_kind: str, seq_length: int, on_gpu: bool
         raise ValueError(f"--doc-mask on a GPU needs --seq-length to be a multiple of 64 (got {seq_length})")
 
 
+def _checkpoint_qk_norm(a: TrainArgs) -> bool:
+    """Whether the checkpoint this run resumes from holds a QK-norm model (its config.json says so): the model is
+    then built with the q_norm / k_norm weights whether or not --qk-norm is given again."""
+    if not a.resume:
+        return False
+    import json
+
+    from .utils.checkpoint import find_checkpoint
+    d = find_checkpoint(a.checkpoint_dir if a.resume == "auto" else a.resume)
+    path = os.path.join(d, "config.json") if d else None
+    if not path or not os.path.isfile(path):
+        return False
+    with open(path) as f:
+        return LlamaConfig.from_dict(json.load(f)).qk_norm
+
+
 def _resolve_data_kind(a: TrainArgs) -> str:
     if a.data != "auto":
         return a.data
@@ -250,6 +269,8 @@ class Trainer:
             from .ops.tuned_gemm import enable_tuned_gemms
             enable_tuned_gemms(e.device)
         self.llama_config: LlamaConfig = resolve_llama_config(a.llama_config_file)
+        if (a.qk_norm or _checkpoint_qk_norm(a)) and not self.llama_config.qk_norm:
+            self.llama_config = dataclasses.replace(self.llama_config, qk_norm=True)
         if str(a.per_device_batch_size).lower() == "auto":
             a.per_device_batch_size = auto_micro_batch(self.llama_config, a.seq_length, a.batch_size, e.device)
         a.per_device_batch_size = int(a.per_device_batch_size)
@@ -497,8 +518,11 @@ class Trainer:
     def save(self, step: int):
         from .utils.checkpoint import save_checkpoint
         ds = self.data.state_dict() if hasattr(self.data, "state_dict") else None
+        extra = {"run_name": self.run_name}
+        if self.llama_config.qk_norm:  # a checkpoint without the key holds a model without QK-norm
+            extra["qk_norm"] = True
         save_checkpoint(self.args.checkpoint_dir, self.model, self.diloco, self.env, step, data_state=ds,
-                        extra={"run_name": self.run_name})
+                        extra=extra)
 
 
 def _fault_spec():
