@@ -97,6 +97,9 @@ class LlamaConfig:
     attention_dropout: float = 0.0
     mlp_bias: bool = False
     qk_norm: bool = False  # per-head RMSNorm of q and k before RoPE (Qwen3), docs/DESIGN.md "QK-norm"
+    # sliding-window attention (Mistral): every layer's query q sees keys q - W + 1 .. q; None / 0 = off
+    # (docs/DESIGN.md "Sliding window")
+    sliding_window: Optional[int] = None
     architectures: Optional[list] = None
     extra: Dict[str, Any] = dataclasses.field(default_factory=dict)
 
@@ -105,6 +108,8 @@ class LlamaConfig:
             self.num_key_value_heads = self.num_attention_heads
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
+        if self.sliding_window == 0:
+            self.sliding_window = None
         # transformers>=5 stores rope_theta inside rope_parameters; accept both spellings.
         rp = self.extra.get("rope_parameters")
         if isinstance(rp, dict) and "rope_theta" in rp:
@@ -121,6 +126,18 @@ class LlamaConfig:
         extra = {k: v for k, v in d.items() if k not in known}
         if d.get("model_type") == "qwen3" or d.get("architectures") == ["Qwen3ForCausalLM"]:
             kw["qk_norm"] = True  # HF Qwen3 has no such key: the architecture implies it
+        # HF Mistral (model_type "mistral" / MistralForCausalLM) is Llama + `sliding_window`: nothing else to map.
+        # HF Qwen2 / Qwen3 carry the window behind a switch and a first windowed layer
+        qwen = str(d.get("model_type", "")).startswith("qwen") or "Qwen" in str((d.get("architectures") or [""])[0])
+        if kw.get("sliding_window") and ("use_sliding_window" in d or qwen):
+            first, nl = int(d.get("max_window_layers") or 0), int(d.get("num_hidden_layers", 0))
+            if not d.get("use_sliding_window", False) or first >= nl:  # HF's default for the switch is False
+                kw["sliding_window"] = None
+            elif first > 0:
+                raise ValueError(f"per-layer sliding windows are not supported (max_window_layers = {first} of {nl} "
+                                 "layers): every layer uses the same window")
+            for k in ("use_sliding_window", "max_window_layers", "layer_types"):
+                extra.pop(k, None)  # derived again by to_hf_json
         return cls(**kw, extra=extra)
 
     @classmethod
@@ -134,6 +151,8 @@ class LlamaConfig:
         d.pop("rope_parameters", None)
         if not self.qk_norm:
             del d["qk_norm"]  # off: the dict is what it always was
+        if not self.sliding_window:
+            del d["sliding_window"]  # likewise
         if d.get("architectures") is None:
             d["architectures"] = ["LlamaForCausalLM"]
         return d
@@ -144,6 +163,10 @@ class LlamaConfig:
         d["model_type"] = "llama"
         if self.qk_norm:  # Llama + QK-norm is HF Qwen3: same tensor names, same math (head_dim is explicit there)
             d["model_type"], d["architectures"], d["head_dim"] = "qwen3", ["Qwen3ForCausalLM"], self.head_dim
+            if self.sliding_window:  # every layer slides: HF derives layer_types = all "sliding_attention"
+                d["use_sliding_window"], d["max_window_layers"] = True, 0
+        elif self.sliding_window:  # Llama + sliding window is HF Mistral: same tensor names and order, same math
+            d["model_type"], d["architectures"], d["head_dim"] = "mistral", ["MistralForCausalLM"], self.head_dim
         d["torch_dtype"] = "float32"
         return d
 
@@ -154,6 +177,9 @@ class LlamaConfig:
             raise ValueError("attention_bias / mlp_bias are not supported (reference uses none)")
         if self.num_attention_heads % self.num_key_value_heads:
             raise ValueError("num_attention_heads must be a multiple of num_key_value_heads")
+        if self.sliding_window is not None and (isinstance(self.sliding_window, bool)
+                                                or not isinstance(self.sliding_window, int) or self.sliding_window < 1):
+            raise ValueError(f"sliding_window must be an integer >= 1 (0 / null = off), got {self.sliding_window!r}")
         if self.rope_scaling not in (None, {}) and self.rope_scaling.get("rope_type", self.rope_scaling.get("type")) not in (
             "default", "linear", "llama3"):
             raise ValueError(f"unsupported rope_scaling {self.rope_scaling}")
@@ -211,6 +237,9 @@ class LlamaConfig:
             if len(s) == 2 and "embed_tokens" not in name:
                 p_mm += s[0] * s[1]
         attn = 12 * L * self.q_size * seq_len / 2  # causal: half the score matrix
+        W = self.sliding_window
+        if W and W < seq_len:  # the visible area of a window: W (2T - W) / 2 scores of T^2 (= T / 2 per token at W = T)
+            attn = 12 * L * self.q_size * W * (2 * seq_len - W) / (2 * seq_len)
         return 6.0 * p_mm + attn
 
 

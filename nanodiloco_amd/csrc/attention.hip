@@ -388,7 +388,13 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // doc_start for the query-parallel kernels (query q sees keys doc_start[q] <= k <= q), doc_end for dK/dV (key k is
 // seen by queries k <= q < doc_end[k]).  doc_start is non-decreasing, so a block's / wave's first query carries its
 // minimum: 64-key tiles wholly before it are neither loaded (block) nor multiplied (wave).
-constexpr int MASK_NONE = 0, MASK_PAD = 1, MASK_DOC = 2;
+// MASK_WIN: a sliding window of `window` >= 1 keys that counts the query itself, composed with an optional per-sequence
+// key start KS [B] (null = 0): query q sees keys max(ks, q - window + 1) <= k <= q.  The bound is arithmetic and
+// monotone, so the mode shares the MASK_PAD code paths and adds the window terms next to every pad term; the tile
+// skipping (LDS-DMA kernels) follows MASK_DOC: key tiles wholly before the block's first window are never loaded,
+// tiles wholly before a wave's first window are not multiplied, dK/dV's query walk ends with the block's last key's
+// window.
+constexpr int MASK_NONE = 0, MASK_PAD = 1, MASK_DOC = 2, MASK_WIN = 3;
 // MASK_DOC keeps no per-lane bound live across the tile loop (the head_dim-64 forward and dK/dV kernels sit exactly
 // on their register budgets): a wave's 32 rows are consecutive tokens, so their bounds are the bound of the
 // document that is open at the wave's edge (one scalar) plus one bit per row -- "a document starts / ends here" --
@@ -419,10 +425,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
                                                           float* __restrict__ LSE, int B, int nh, int nkv, int T,
                                                           int64_t ld, int64_t ldo, float scale,
                                                           const float* __restrict__ cosT, const float* __restrict__ sinT,
-                                                          const int* __restrict__ KS, float thr, int order) {
+                                                          const int* __restrict__ KS, float thr, int order,
+                                                          int window = 0) {
   constexpr int BN = 64, NT = HD / 16, NO = HD / 32;
-  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC;
+  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC, WIN = MASK == MASK_WIN;
   static_assert(!DOC || (DMA && ABL == 0 && NW == 4), "document mask: default LDS-DMA kernel, plain softmax variant");
+  static_assert(!WIN || (!ROPE && ABL == 0 && NW == 4), "sliding window: default block shape, plain softmax variant");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * BN * HD];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[2 * BN * HD];
 
@@ -445,11 +453,14 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
     bh = blockIdx.x % bh_count;
   }
   const int b = bh / nh, head = bh % nh, kvh = head / (nh / nkv);
-  const int ks = PAD ? KS[b] : 0;  // PAD (left-padded batch): keys < ks are masked for every query
+  // PAD (left-padded batch): keys < ks are masked for every query; WIN: the same, KS optional
+  const int ks = PAD ? KS[b] : (WIN && KS) ? KS[b] : 0;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c32 = lane & 31;
   const int g = lane >> 4, i16 = lane & 15;
-  // DOC: the wave's first query as a scalar, so that the per-tile skip / boundary tests are scalar branches
-  const int q0w = qb * QB + (DOC ? __builtin_amdgcn_readfirstlane(w) : w) * 32, qi = q0w + c32;
+  // DOC / WIN: the wave's first query as a scalar, so that the per-tile skip / boundary tests are scalar branches
+  const int q0w = qb * QB + ((DOC || WIN) ? __builtin_amdgcn_readfirstlane(w) : w) * 32, qi = q0w + c32;
+  // WIN: the first key any query of the wave sees (its first query's window start, or the key start)
+  const int wlo = WIN ? max(ks, q0w - window + 1) : 0;
   // DOC: dsw0 / dsw1 = document start of the wave's first / last query (the wave's minimum / maximum)
   int dsw0 = 0, dsw1 = 0;
   DocWave dw{0, 0};
@@ -480,6 +491,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
   // doc_start[t] <= t invariant must not move the loads out of the sequence); the buffer parity counts from it
   int j0 = 0;
   if constexpr (DOC) j0 = min(max(__builtin_amdgcn_readfirstlane(KS[(int64_t)b * T + qb * QB]), 0) / BN, ntiles - 1);
+  // WIN: the first tile that holds a key of the block's first query's window (LDS-DMA kernel; the register-staged
+  // one walks every tile and only masks)
+  if constexpr (WIN && DMA) j0 = min(max(max(ks, qb * QB - window + 1), 0) / BN, ntiles - 1);
   typename std::conditional<ROPE, StageRope<BN, HD>, Stage<BN, HD>>::type sk;
   Stage<BN, HD> sv;
   TileDma<HD, BN, NW, DOC> tdma;
@@ -525,8 +539,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
       if constexpr (!(ABL & 1)) if (j + 1 < ntiles) dma_issue(j + 1, PAR ^ 1);
       ND_STAMP(stp.mark(2);)
     }
-    // else: whole tile above this wave's diagonal, or (DOC) before its first query's document (wave-uniform)
-    if (k0 <= q0w + 31 && (!DOC || k0 + BN > dsw0)) {
+    // else: whole tile above this wave's diagonal, or (DOC / WIN) before its first query's document / window
+    // (wave-uniform)
+    if (k0 <= q0w + 31 && (!DOC || k0 + BN > dsw0) && (!WIN || k0 + BN > wlo)) {
       // K row fragments issued up front (V^T transposing reads stay next to their MFMAs: holding
       // them too costs the third wave per SIMD)
       bf16x8 ka[2][NT];
@@ -597,6 +612,18 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
                 if (!(vis & (1u << ((r & 3) + 8 * (r >> 2))))) s[kt][r] = -INFINITY;
             }
           }
+        } else if constexpr (WIN) {
+          // the tile crosses the diagonal, starts before the window of the wave's LAST query, or before the key start
+          if ((k0 + BN - 1 > q0w) || (k0 + BN > T) || k0 < q0w + 32 - window || k0 < ks) {
+            const int lo = max(ks, qi - window + 1);
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (key > qi || key >= T || key < lo) s[kt][r] = -INFINITY;
+              }
+          }
         } else if ((k0 + BN - 1 > q0w) || (k0 + BN > T) || (PAD && k0 < ks)) {
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt)
@@ -618,8 +645,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
       // Both lanes of a query pair see the same m / mx, so l and O get one consistent factor.
       const bool upd = mx > m + thr;
       const float mnew = upd ? mx : m;
-      // a row with no visible key yet (a left-pad query, or a tile before the query's document: every key
-      // masked) keeps p = 0, l = 0
+      // a row with no visible key yet (a left-pad query, or a tile before the query's document / window: every
+      // key masked) keeps p = 0, l = 0
       const float mref = (MASK != MASK_NONE && mnew == -INFINITY) ? 0.f : mnew;
       const float alpha = upd ? fexp2(m - mref) : 1.f;
       m = mnew;
@@ -739,10 +766,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
                                                              const bf16_t* __restrict__ O = nullptr,
                                                              float* __restrict__ NL = nullptr,
                                                              float* __restrict__ ND = nullptr,
-                                                             const int* __restrict__ KS = nullptr, int order = 0) {
+                                                             const int* __restrict__ KS = nullptr, int order = 0,
+                                                             int window = 0) {
   constexpr int BN = 64, NT = HD / 16, NO = HD / 32;
-  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC;
+  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC, WIN = MASK == MASK_WIN;
   static_assert(!DOC || (DMA && PRE), "document mask: fused LDS-DMA backward only");
+  static_assert(!WIN || (DMA && PRE && NW == 4), "sliding window: fused LDS-DMA backward, default block shape");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * BN * HD];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[2 * BN * HD];
 
@@ -761,10 +790,11 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
     bh = blockIdx.x % bh_count;
   }
   const int b = bh / nh, head = bh % nh, kvh = head / (nh / nkv);
-  const int ks = PAD ? KS[b] : 0;
+  const int ks = PAD ? KS[b] : (WIN && KS) ? KS[b] : 0;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c32 = lane & 31;
   const int g = lane >> 4, i16 = lane & 15;
-  const int q0w = qb * QB + (DOC ? __builtin_amdgcn_readfirstlane(w) : w) * 32, qi = q0w + c32;
+  const int q0w = qb * QB + ((DOC || WIN) ? __builtin_amdgcn_readfirstlane(w) : w) * 32, qi = q0w + c32;
+  const int wlo = WIN ? max(ks, q0w - window + 1) : 0;  // see attn_fwd_kernel
   int dsw0 = 0, dsw1 = 0;  // see attn_fwd_kernel
   DocWave dw{0, 0};
   if constexpr (DOC) {
@@ -819,6 +849,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
   const int ntiles = (min(T, qb * QB + QB) + BN - 1) / BN;
   int j0 = 0;  // see attn_fwd_kernel
   if constexpr (DOC) j0 = min(max(__builtin_amdgcn_readfirstlane(KS[(int64_t)b * T + qb * QB]), 0) / BN, ntiles - 1);
+  if constexpr (WIN) j0 = min(max(max(ks, qb * QB - window + 1), 0) / BN, ntiles - 1);
   typename std::conditional<ROPE, StageRope<BN, HD>, Stage<BN, HD>>::type sk;
   Stage<BN, HD> sv;
   TileDma<HD, BN, NW, DOC> tdma;
@@ -856,12 +887,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
       if (j + 1 < ntiles) dma_issue(j + 1);
       ND_STAMP(stp.mark(2);)
     }
-    if (k0 <= q0w + 31 && (!DOC || k0 + BN > dsw0)) {  // DOC: else the tile lies before the wave's first document
-      const bool diag = (k0 + BN - 1 > q0w) || (k0 + BN > T) || (qi >= T) || (PAD && k0 < ks) || (DOC && k0 < dsw1);
+    // DOC / WIN: else the tile lies before the wave's first document / window
+    if (k0 <= q0w + 31 && (!DOC || k0 + BN > dsw0) && (!WIN || k0 + BN > wlo)) {
+      const bool diag = (k0 + BN - 1 > q0w) || (k0 + BN > T) || (qi >= T) || (PAD && k0 < ks) || (DOC && k0 < dsw1) ||
+                        (WIN && (k0 < q0w + 32 - window || k0 < ks));
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         if (k0 + kt * 32 > q0w + 31) continue;  // this 32-key half is above the wave's diagonal
         if (DOC && k0 + kt * 32 + 32 <= dsw0) continue;  // ... or before the wave's first document
+        if (WIN && k0 + kt * 32 + 32 <= wlo) continue;   // ... or before the wave's first window
         ND_STAMP(stp.mark(7);)
         // fragments issued up front (row reads for S^T / dP^T, transposing reads for dQ)
         bf16x8 ka[NT], va[NT], tk[2][NO];
@@ -895,10 +929,11 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
             dp[r] = p * (dp[r] - dlt);
           }
         } else {
+          const int lo = WIN ? max(ks, qi - window + 1) : ks;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float p = (key <= qi && key < T && qi < T && (!PAD || key >= ks)) ? fexp2(fmaf(s[r], c, -lse)) : 0.f;
+            const float p = (key <= qi && key < T && qi < T && (!(PAD || WIN) || key >= lo)) ? fexp2(fmaf(s[r], c, -lse)) : 0.f;
             dp[r] = p * (dp[r] - dlt);
           }
         }
@@ -1266,6 +1301,39 @@ ND_API int nd_attn_fwd_doc(const void* q, const void* k, const void* v, void* o,
   }
 }
 
+// Sliding-window forward: query q attends to keys max(ks[b], q - window + 1) <= k <= q (window >= 1 counts the query
+// itself; ks: optional per-sequence key start as in nd_attn_fwd_ks, nullptr = 0).  q|k already rotated (cosT / sinT
+// must be null).  T % 64 == 0: the LDS-DMA kernel, which neither loads the key tiles before a block's first window
+// nor multiplies those before a wave's; any other T: the register-staged kernel with the per-score mask only.
+// Always the default block shape and the plain softmax variant; the A/B switches of AttnEnv do not apply.
+template <int HD>
+static int fwd_win_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int nh, int nkv,
+                          int T, int64_t ld, int64_t ldo, float scale, const int* ks, int window, hipStream_t s) {
+  const dim3 g((T + 127) / 128 * B * nh), b(256);
+  if (T % 64 == 0)
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, false, true, MASK_WIN>), g, b, 0, s, (const bf16_t*)q, (const bf16_t*)k,
+                       (const bf16_t*)v, (bf16_t*)o, lse, B, nh, nkv, T, ld, ldo, scale, nullptr, nullptr, ks,
+                       g_attn.thr, attn_order(), window);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, false, false, MASK_WIN>), g, b, 0, s, (const bf16_t*)q, (const bf16_t*)k,
+                       (const bf16_t*)v, (bf16_t*)o, lse, B, nh, nkv, T, ld, ldo, scale, nullptr, nullptr, ks,
+                       g_attn.thr, attn_order(), window);
+  ND_LAUNCH_CHECK();
+}
+
+ND_API int nd_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int nh, int nkv,
+                           int T, int hd, int64_t ld, int64_t ldo, const float* cosT, const float* sinT, float scale,
+                           const int* ks, int window, hipStream_t s) {
+  if (nh % nkv || (ld % 8) || (ldo % 8) || window < 1 || T < 1 || cosT || sinT) return (int)hipErrorInvalidValue;
+  window = window < T ? window : T;  // a window of T or more keys is the whole prefix
+  switch (hd) {
+    case 32: return fwd_win_launch<32>(q, k, v, o, lse, B, nh, nkv, T, ld, ldo, scale, ks, window, s);
+    case 64: return fwd_win_launch<64>(q, k, v, o, lse, B, nh, nkv, T, ld, ldo, scale, ks, window, s);
+    case 128: return fwd_win_launch<128>(q, k, v, o, lse, B, nh, nkv, T, ld, ldo, scale, ks, window, s);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
 ND_API int nd_attn_bwd_pre(const void* o, const void* dout, float* delta, int B, int nh, int T, int64_t hd,
                            int64_t ldo, hipStream_t s) {
   const int64_t threads = (int64_t)B * T * nh * (hd / 8);
@@ -1307,13 +1375,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ NL, const float* __restrict__ ND, bf16_t* __restrict__ dK,
     bf16_t* __restrict__ dV, int B, int nh, int nkv, int T, int64_t ld, int64_t ldo, float scale,
-    const float* __restrict__ cosT, const float* __restrict__ sinT, const int* __restrict__ KS, int order) {
+    const float* __restrict__ cosT, const float* __restrict__ sinT, const int* __restrict__ KS, int order,
+    int window = 0) {
   constexpr int NT = HD / 16, NO = HD / 32;
   constexpr int CPR = HD / 8;              // 16-B chunks per row
   constexpr int RPI = 64 / CPR;            // rows per 1-KiB DMA wave-instruction
   constexpr int IPW = (BQ / RPI) / NW;     // DMA instructions per wave per operand tile
   constexpr int KB = 32 * NW;              // keys per workgroup
-  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC;
+  constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC, WIN = MASK == MASK_WIN;
+  static_assert(!WIN || (NW == 4 && ABL == 0 && NB == 2), "sliding window: default block shape");
   __shared__ __attribute__((aligned(16))) bf16_t Qs[NB * BQ * HD];
   __shared__ __attribute__((aligned(16))) bf16_t dOs[NB * BQ * HD];
   __shared__ __attribute__((aligned(16))) float lse_s[NB * BQ];
@@ -1330,10 +1400,10 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
     bk = blockIdx.x % bk_count;
   }
   const int b = bk / nkv, kvh = bk % nkv;
-  const int ks = PAD ? KS[b] : 0;
+  const int ks = PAD ? KS[b] : (WIN && KS) ? KS[b] : 0;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c32 = lane & 31;
   const int g = lane >> 4, i16 = lane & 15;
-  const int kw0 = kb * KB + (DOC ? __builtin_amdgcn_readfirstlane(w) : w) * 32, key = kw0 + c32;
+  const int kw0 = kb * KB + ((DOC || WIN) ? __builtin_amdgcn_readfirstlane(w) : w) * 32, key = kw0 + c32;
   // DOC: one past the last query that sees this key; dew0 / dew1 = the wave's first / last key's (doc_end is
   // non-decreasing like doc_start: its minimum / maximum)
   int dew0 = 0, dew1 = 0;
@@ -1382,6 +1452,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
   int qend = T;
   if constexpr (DOC)
     qend = min(max(__builtin_amdgcn_readfirstlane(KS[(int64_t)b * T + min(kb * KB + KB, T) - 1]), qstart + 1), T);
+  // WIN: key k is seen by queries k <= q < k + window; the walk ends with the block's last key's window
+  // (window <= T, launcher: no overflow; qend > qstart since window >= 1)
+  if constexpr (WIN) qend = min(T, min(kb * KB + KB, T) - 1 + window);
   const int ntq = (qend - qstart + BQ - 1) / BQ;
   const int nit = ntq * rep;
   // order bit 1: walk the query tiles from the LAST one down to the diagonal.  Every key block of a head
@@ -1455,6 +1528,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
       const int qsub = q0 + qs * 32;
       if (kw0 > qsub + 31 || kw0 >= T) continue;  // wave-uniform: no query >= any of our keys
       if (DOC && qsub >= dew1) continue;          // wave-uniform: every query past our last key's document
+      if (WIN && qsub >= kw0 + 31 + window) continue;  // wave-uniform: every query past our last key's window
       // All LDS fragments of this step are issued up front (row reads for S / dP, transposing reads
       // for dV / dK) so their latency hides behind the MFMA chains and the softmax VALU instead of
       // being exposed one s_waitcnt at a time.
@@ -1498,7 +1572,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
         }
       }
       ND_STAMP(stp.mark(3);)
-      const bool diag = (kw0 + 31 > qsub) || (qsub + 31 >= T) || (key >= T) || (PAD && kw0 < ks) || (DOC && qsub + 31 >= dew0);
+      const bool diag = (kw0 + 31 > qsub) || (qsub + 31 >= T) || (key >= T) || (PAD && kw0 < ks) || (DOC && qsub + 31 >= dew0) ||
+                        (WIN && (qsub + 31 >= kw0 + window || kw0 < ks));  // WIN: reaches the FIRST key's window end
       if constexpr ((ABL & 4) != 0) {
       } else if (!diag) {
 #pragma unroll
@@ -1520,7 +1595,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int qq = qsub + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const float p = (key <= qq && qq < T && key < T && (!PAD || key >= ks)) ? fexp2(s[r] * c) : 0.f;
+          const float p = (key <= qq && qq < T && key < T && (!(PAD || WIN) || key >= ks) && (!WIN || qq < key + window))
+                              ? fexp2(s[r] * c) : 0.f;
           s[r] = p;
           dp[r] = p * dp[r];
         }
@@ -1757,6 +1833,53 @@ ND_API int nd_attn_bwd_fused_doc(const void* q, const void* k, const void* v, co
     ND_BD(64)
     ND_BD(128)
 #undef ND_BD
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+// Sliding-window fused backward (see nd_attn_fwd_win): dQ walks the key tiles from its block's first window, dK/dV
+// walks the query tiles up to the end of its block's last key's window.  LDS-DMA kernels, default block shapes:
+// T % 64 == 0, rope_mode 0 or 2; no atomics, bitwise reproducible like the other modes.
+template <int HD, bool ROPE_OUT>
+static int bwd_fused_win_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, void* dq, void* dk, void* dv, float* ws, int B, int nh, int nkv,
+                                int T, int64_t ld, int64_t ldo, const float* cosT, const float* sinT, float scale,
+                                const int* ks, int window, hipStream_t s) {
+  const int nb = (T + 127) / 128;
+  const int64_t n = (int64_t)B * nh * T;
+  float *nl = ws, *nd = ws + n;
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, false, ROPE_OUT, true, true, MASK_WIN>), dim3(nb * B * nh), dim3(256), 0, s,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse, nullptr,
+                     (bf16_t*)dq, B, nh, nkv, T, ld, ldo, scale, cosT, sinT, (const bf16_t*)o, nl, nd, ks,
+                     attn_order(), window);
+  if (T % 128 == 0)
+    hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<HD, ROPE_OUT, 128, MASK_WIN>), dim3(nb * B * nkv), dim3(256), 0, s,
+                       (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, nl, nd, (bf16_t*)dk,
+                       (bf16_t*)dv, B, nh, nkv, T, ld, ldo, scale, cosT, sinT, ks, dkdv_order(nh, nkv), window);
+  else
+    hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<HD, ROPE_OUT, 64, MASK_WIN>), dim3(nb * B * nkv), dim3(256), 0, s,
+                       (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, nl, nd, (bf16_t*)dk,
+                       (bf16_t*)dv, B, nh, nkv, T, ld, ldo, scale, cosT, sinT, ks, dkdv_order(nh, nkv), window);
+  ND_LAUNCH_CHECK();
+}
+
+ND_API int nd_attn_bwd_fused_win(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                 const float* lse, void* dq, void* dk, void* dv, float* ws, int B, int nh, int nkv,
+                                 int T, int hd, int64_t ld, int64_t ldo, const float* cosT, const float* sinT,
+                                 float scale, int rope_mode, const int* ks, int window, hipStream_t s) {
+  if (nh % nkv || (ld % 8) || (ldo % 8) || T < 1 || T % 64 || ws == nullptr || window < 1)
+    return (int)hipErrorInvalidValue;
+  if ((rope_mode != 0 && rope_mode != 2) || (rope_mode == 2 && !(cosT && sinT))) return (int)hipErrorInvalidValue;
+  window = window < T ? window : T;
+  switch (hd) {
+#define ND_BW(H)                                                                                                     \
+  case H:                                                                                                            \
+    return (rope_mode == 2 ? bwd_fused_win_launch<H, true> : bwd_fused_win_launch<H, false>)(                        \
+        q, k, v, o, dout, lse, dq, dk, dv, ws, B, nh, nkv, T, ld, ldo, cosT, sinT, scale, ks, window, s);
+    ND_BW(32)
+    ND_BW(64)
+    ND_BW(128)
+#undef ND_BW
     default: return (int)hipErrorInvalidValue;
   }
 }

@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(64 * DEC_WAVES)
 attn_decode_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ cosT, const float* __restrict__ sinT,
                    const int* __restrict__ pos, const int* __restrict__ kstart, bf16_t* __restrict__ kcache,
                    bf16_t* __restrict__ vcache, float* __restrict__ part_o, float* __restrict__ part_ml, int nh,
-                   int nkv, int rep, int S_max, int64_t ld, float scale2) {
+                   int nkv, int rep, int S_max, int64_t ld, float scale2, int window) {
   constexpr int LPR = HD / 8;       // lanes per K/V row
   constexpr int KPI = 64 / LPR;     // rows per wave-wide load
   constexpr int ITER = KPW / KPI;   // loads per lane for the wave's keys
@@ -80,7 +80,8 @@ attn_decode_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ cos
   const int g = blockIdx.x, b = blockIdx.y, c = blockIdx.z;
   const int nchunks = gridDim.z;
   const int p = pos[b];
-  const int ks = kstart ? max(kstart[b], 0) : 0;
+  // window > 0 (sliding window, counts the query): keys below p - window + 1 are out of sight like those below kstart
+  const int ks = max(kstart ? max(kstart[b], 0) : 0, (window > 0 && (unsigned)p < (unsigned)S_max) ? p - window + 1 : 0);
   const int64_t pbase = ((int64_t)(b * nkv + g) * nchunks + c) * rep;  // this workgroup's first partial row
   const int c0 = c * SPLIT;
   const bool holds_p = c0 <= p && p < c0 + SPLIT;  // this workgroup appends (even when kstart leaves it no key)
@@ -251,12 +252,12 @@ attn_decode_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ cos
 __global__ void attn_decode_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                            const int* __restrict__ pos, const int* __restrict__ kstart,
                                            bf16_t* __restrict__ o, int nh, int nkv, int rep, int hd, int nchunks,
-                                           int S_max) {
+                                           int S_max, int window) {
   const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
   const int g = h / rep, r = h % rep;
   const int64_t base = (int64_t)(b * nkv + g) * nchunks * rep + r;  // + c * rep: chunk c's partial row
   const int p = pos[b];
-  const int ks = kstart ? max(kstart[b], 0) : 0;
+  const int ks = max(kstart ? max(kstart[b], 0) : 0, (window > 0 && (unsigned)p < (unsigned)S_max) ? p - window + 1 : 0);  // see attn_decode_kernel
   float M = -INFINITY, L = 0.f, O = 0.f;
   if ((unsigned)p < (unsigned)S_max && ks <= p) {
     const int c_lo = ks / SPLIT, c_hi = p / SPLIT;  // c_hi < nchunks: p < S_max
@@ -279,11 +280,11 @@ __global__ void attn_decode_combine_kernel(const float* __restrict__ part_o, con
 template <int HD>
 int launch(const bf16_t* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart, bf16_t* kc,
            bf16_t* vc, float* part_o, float* part_ml, int B, int nh, int nkv, int rep, int S_max, int64_t ld,
-           float scale2, hipStream_t st) {
+           float scale2, int window, hipStream_t st) {
   const dim3 grid((unsigned)nkv, (unsigned)B, (unsigned)((S_max + SPLIT - 1) / SPLIT)), block(64 * DEC_WAVES);
 #define ND_DECODE(R)                                                                                            \
   hipLaunchKernelGGL((attn_decode_kernel<HD, R>), grid, block, 0, st, qkv, cosT, sinT, pos, kstart, kc, vc, part_o, \
-                     part_ml, nh, nkv, rep, S_max, ld, scale2)
+                     part_ml, nh, nkv, rep, S_max, ld, scale2, window)
   if (rep == 1) ND_DECODE(1);
   else if (rep == 2) ND_DECODE(2);
   else if (rep <= 4) ND_DECODE(4);
@@ -300,9 +301,10 @@ ND_API int nd_attn_decode_split() { return SPLIT; }
 // Workspace: part_o [B, nkv, nchunks, rep, hd] fp32, part_ml [B, nkv, nchunks, rep, 2] fp32, nchunks = ceil(S_max / SPLIT).
 // `ld`: row stride of qkv in elements.  The tables must hold at least S_max rows; 0 <= pos[b] < S_max (a position
 // outside writes nothing and gives o = 0).
-ND_API int nd_attn_decode(const void* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart,
-                          void* kcache, void* vcache, float* part_o, float* part_ml, void* o, int B, int nh, int nkv,
-                          int hd, int S_max, int64_t ld, float scale, hipStream_t st) {
+// window: 0 = none; W >= 1 = sliding window, keys max(kstart[b], pos[b] - W + 1) .. pos[b] (nd_attn_decode_win).
+static int decode_impl(const void* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart,
+                       void* kcache, void* vcache, float* part_o, float* part_ml, void* o, int B, int nh, int nkv,
+                       int hd, int S_max, int64_t ld, float scale, int window, hipStream_t st) {
   if (B < 1 || B > 65535 || nh < 1 || nkv < 1 || nkv > 65535 || nh % nkv || nh / nkv > 8 || S_max < 1 ||
       (S_max + SPLIT - 1) / SPLIT > 65535)
     return (int)hipErrorInvalidValue;
@@ -320,12 +322,31 @@ ND_API int nd_attn_decode(const void* qkv, const float* cosT, const float* sinT,
   bf16_t* kc = reinterpret_cast<bf16_t*>(kcache);
   bf16_t* vc = reinterpret_cast<bf16_t*>(vcache);
   int err;
-  if (hd == 32) err = launch<32>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, st);
-  else if (hd == 64) err = launch<64>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, st);
-  else err = launch<128>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, st);
+  if (hd == 32) err = launch<32>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st);
+  else if (hd == 64) err = launch<64>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st);
+  else err = launch<128>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st);
   if (err) return err;
   const int nchunks = (S_max + SPLIT - 1) / SPLIT;
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)nh, (unsigned)B), dim3((unsigned)hd), 0, st, part_o,
-                     part_ml, pos, kstart, reinterpret_cast<bf16_t*>(o), nh, nkv, rep, hd, nchunks, S_max);
+                     part_ml, pos, kstart, reinterpret_cast<bf16_t*>(o), nh, nkv, rep, hd, nchunks, S_max, window);
   ND_LAUNCH_CHECK();
+}
+
+ND_API int nd_attn_decode(const void* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart,
+                          void* kcache, void* vcache, float* part_o, float* part_ml, void* o, int B, int nh, int nkv,
+                          int hd, int S_max, int64_t ld, float scale, hipStream_t st) {
+  return decode_impl(qkv, cosT, sinT, pos, kstart, kcache, vcache, part_o, part_ml, o, B, nh, nkv, hd, S_max, ld, scale,
+                     0, st);
+}
+
+// Sliding-window decode step: as nd_attn_decode over keys max(kstart[b], pos[b] - window + 1, 0) .. pos[b], window >= 1.
+// Chunks wholly below that bound write the empty partial and leave; the combine reads only the chunks that meet the
+// range, so a step reads O(window) keys.  The append to slot pos[b] and the key-indexed partition are unchanged: the
+// result is bitwise nd_attn_decode's with kstart' = max(kstart, pos - window + 1).
+ND_API int nd_attn_decode_win(const void* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart,
+                              void* kcache, void* vcache, float* part_o, float* part_ml, void* o, int B, int nh,
+                              int nkv, int hd, int S_max, int64_t ld, float scale, int window, hipStream_t st) {
+  if (window < 1) return (int)hipErrorInvalidValue;
+  return decode_impl(qkv, cosT, sinT, pos, kstart, kcache, vcache, part_o, part_ml, o, B, nh, nkv, hd, S_max, ld, scale,
+                     window, st);
 }

@@ -55,6 +55,10 @@ def parse_args(argv: Optional[List[str]] = None) -> TrainArgs:
     ns = parser.parse_args(argv)
     if ns.doc_mask and ns.data == "hf":
         parser.error("--doc-mask is for packed data (--data memmap | synthetic), not --data hf")
+    if ns.sliding_window < 0:
+        parser.error("--sliding-window must be >= 1 (0 = off)")
+    if ns.sliding_window and ns.doc_mask:
+        parser.error("--sliding-window and --doc-mask cannot be combined")
     return TrainArgs(**vars(ns))
 
 

@@ -75,6 +75,8 @@ class LlamaForCausalLM:
         self.config = config
         # packed windows: attention stays inside each EOS-separated document (ops.doc_bounds)
         self.doc_mask = bool(doc_mask)
+        if self.doc_mask and config.sliding_window:
+            raise ValueError("doc_mask (packed documents) and a sliding window cannot be combined")
         self.debug_checks = False  # validate the derived bounds every forward (host sync: never under graph capture)
         # z-loss coefficient of the training objective (--z-loss; ops/cross_entropy.py): 0.0 = off.  A hyperparameter,
         # not state; evaluation (loss_stats) ignores it
@@ -177,7 +179,7 @@ class LlamaForCausalLM:
                                             c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps,
                                             inplace=True)
         o = ops.attention(qkv, cos, sin, B, T, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
-                          inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc)
+                          inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc, window=c.sliding_window)
         if cache is not None:
             # prefill: the HIP path has rotated q|k inside qkv by now (in place, or in the GEMM epilogue); the
             # PyTorch path leaves its input alone and cache_fill rotates k itself

@@ -154,11 +154,15 @@ def _declare(L: ctypes.CDLL):
         # document-masked (packed windows): the _ks signatures with (doc_start, doc_end) in place of ks
         "nd_attn_fwd_doc": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P, P, P],
         "nd_attn_bwd_fused_doc": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, P, P],
+        # sliding window (+ optional key start): ..., ks, window, stream
+        "nd_attn_fwd_win": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P, I, P],
+        "nd_attn_bwd_fused_win": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, I, P],
         "nd_attn_bwd_pre": [P, P, P, I, I, I, L64, L64, P],
         "nd_attn_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
         "nd_attn_bwd_fused": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
         # single-query attention against a KV cache, RoPE + append fused, split-KV + combine (csrc/attn_decode.hip)
         "nd_attn_decode": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, P],
+        "nd_attn_decode_win": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, I, P],
         "nd_attn_decode_split": [],
         # mlp
         "nd_swiglu_fwd": [P, P, I, L64, I, P],

@@ -15,6 +15,8 @@ backward kernels' store epilogues, so the backward needs no extra pass)
 Packed windows (several EOS-separated documents per sequence): ``doc_bounds`` gives every token the bounds of its
 document and ``attention(..., doc_bounds=...)`` runs ``nd_attn_fwd_doc`` / ``nd_attn_bwd_fused_doc`` -- block-diagonal
 causal attention in the same kernels, which skip the key / query tiles that lie wholly outside a block's documents.
+Sliding window (``attention(..., window=W)``, W < T): ``nd_attn_fwd_win`` / ``nd_attn_bwd_fused_win`` -- query q sees keys
+max(kstart, q - W + 1) .. q; the LDS-DMA kernels skip the key / query tiles that lie wholly outside a block's windows.
 GQA (nkv < nh) is handled by head-index mapping inside the kernels (no K/V repetition).
 """
 from __future__ import annotations
@@ -62,7 +64,8 @@ class FlashAttnFn(torch.autograd.Function):
     their store epilogues (rope_mode 2), so the gradient returned is w.r.t. the raw projection."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, B, T, nh, nkv, hd, kstart=None, rotated=False, doc_start=None, doc_end=None):
+    def forward(ctx, qkv, cos, sin, B, T, nh, nkv, hd, kstart=None, rotated=False, doc_start=None, doc_end=None,
+                window=None):
         ld = qkv.shape[1]
         if not rotated:  # else the projection GEMM's epilogue already rotated q|k
             _rope(qkv, cos, sin, B, T, nh, nkv, hd, inverse=False)
@@ -72,7 +75,11 @@ class FlashAttnFn(torch.autograd.Function):
         lse = torch.empty(B, nh, T, dtype=torch.float32, device=qkv.device)
         L = _ext.lib()
         ks = _ext.ptr(kstart) if kstart is not None else 0
-        if doc_start is not None:
+        if window is not None:  # a real window (< T): ops.attention never passes another
+            _ext.check(L.nd_attn_fwd_win(_ext.ptr(qkv), _ext.ptr(k), _ext.ptr(v), _ext.ptr(o), _ext.ptr(lse),
+                                         B, nh, nkv, T, hd, ld, nh * hd, 0, 0, float(hd ** -0.5), ks, int(window),
+                                         _ext.stream_ptr(qkv.device)), "nd_attn_fwd_win")
+        elif doc_start is not None:
             _ext.check(L.nd_attn_fwd_doc(_ext.ptr(qkv), _ext.ptr(k), _ext.ptr(v), _ext.ptr(o), _ext.ptr(lse),
                                          B, nh, nkv, T, hd, ld, nh * hd, 0, 0, float(hd ** -0.5), _ext.ptr(doc_start),
                                          _ext.ptr(doc_end), _ext.stream_ptr(qkv.device)), "nd_attn_fwd_doc")
@@ -83,6 +90,7 @@ class FlashAttnFn(torch.autograd.Function):
         ctx.save_for_backward(qkv, o, lse, cos, sin)
         ctx.kstart = kstart
         ctx.doc = (doc_start, doc_end) if doc_start is not None else None
+        ctx.window = window
         ctx.dims = (B, T, nh, nkv, hd)
         return o
 
@@ -95,6 +103,19 @@ class FlashAttnFn(torch.autograd.Function):
         L = _ext.lib()
         dev = do.device
         ks = _ext.ptr(ctx.kstart) if ctx.kstart is not None else 0
+        if ctx.window is not None:  # sliding window: the fused LDS-DMA backward is the only one
+            if T % 64:
+                raise ValueError(f"sliding-window attention has no backward for T % 64 != 0 (T = {T})")
+            dqkv = torch.empty_like(qkv)
+            k, v = qkv[:, nh * hd:], qkv[:, (nh + nkv) * hd:]
+            dk, dv = dqkv[:, nh * hd:], dqkv[:, (nh + nkv) * hd:]
+            ws = torch.empty(2, B, nh, T, dtype=torch.float32, device=dev)
+            _ext.check(L.nd_attn_bwd_fused_win(_ext.ptr(qkv), _ext.ptr(k), _ext.ptr(v), _ext.ptr(o), _ext.ptr(do),
+                                               _ext.ptr(lse), _ext.ptr(dqkv), _ext.ptr(dk), _ext.ptr(dv), _ext.ptr(ws),
+                                               B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
+                                               float(hd ** -0.5), 2, ks, int(ctx.window), _ext.stream_ptr(dev)),
+                       "nd_attn_bwd_fused_win")
+            return (dqkv,) + (None,) * 12
         if ctx.doc is not None:  # document mode: the fused LDS-DMA backward is the only one
             dqkv = torch.empty_like(qkv)
             k, v = qkv[:, nh * hd:], qkv[:, (nh + nkv) * hd:]
@@ -105,7 +126,7 @@ class FlashAttnFn(torch.autograd.Function):
                                                B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
                                                float(hd ** -0.5), 2, _ext.ptr(ctx.doc[0]), _ext.ptr(ctx.doc[1]),
                                                _ext.stream_ptr(dev)), "nd_attn_bwd_fused_doc")
-            return (dqkv,) + (None,) * 11
+            return (dqkv,) + (None,) * 12
         if _FUSED_STATS["enabled"] and T % 64 == 0:
             # dQ kernel computes delta = rowsum(dO * O) itself and seeds the dK/dV kernel
             dqkv = torch.empty_like(qkv)
@@ -116,7 +137,7 @@ class FlashAttnFn(torch.autograd.Function):
                                               _ext.ptr(lse), _ext.ptr(dqkv), _ext.ptr(dk), _ext.ptr(dv), _ext.ptr(ws),
                                               B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
                                               float(hd ** -0.5), 2, ks, _ext.stream_ptr(dev)), "nd_attn_bwd_fused_ks")
-            return (dqkv,) + (None,) * 11
+            return (dqkv,) + (None,) * 12
         delta = torch.empty(B, nh, T, dtype=torch.float32, device=dev)
         _ext.check(L.nd_attn_bwd_pre(_ext.ptr(o), _ext.ptr(do), _ext.ptr(delta), B, nh, T, hd, nh * hd,
                                      _ext.stream_ptr(dev)), "nd_attn_bwd_pre")
@@ -128,7 +149,7 @@ class FlashAttnFn(torch.autograd.Function):
                                     _ext.ptr(delta), _ext.ptr(dqkv), _ext.ptr(dk), _ext.ptr(dv), _ext.ptr(ws),
                                     B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin), float(hd ** -0.5), 2,
                                     ks, _ext.stream_ptr(dev)), "nd_attn_bwd_ks")
-        return (dqkv,) + (None,) * 11
+        return (dqkv,) + (None,) * 12
 
 
 def key_start(attention_mask: torch.Tensor) -> torch.Tensor:
@@ -196,7 +217,7 @@ def check_doc_bounds(doc_start: torch.Tensor, doc_end: torch.Tensor) -> None:
 
 def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T: int, nh: int, nkv: int,
               hd: int, inplace: bool = False, kstart: torch.Tensor = None, rotated: bool = False,
-              doc_bounds: Tuple[torch.Tensor, torch.Tensor] = None) -> torch.Tensor:
+              doc_bounds: Tuple[torch.Tensor, torch.Tensor] = None, window: int = None) -> torch.Tensor:
     """Causal self-attention with RoPE; qkv [B*T, (nh+2nkv)*hd] -> [B*T, nh*hd].
 
     ``kstart`` (int32 [B], from :func:`key_start`) masks left padding: real queries (t >= kstart[b])
@@ -207,9 +228,18 @@ def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T
     ops/linear.py LinearRopeFn); the backward still returns the gradient w.r.t. the un-rotated q|k.
     ``doc_bounds`` ((doc_start, doc_end) from :func:`doc_bounds`): block-diagonal causal attention for packed
     windows -- query q attends to keys doc_start[b, q] <= k <= q.  RoPE positions are not reset at document starts
-    (scores depend on q - k only).  Not combinable with ``kstart``; the HIP path needs T % 64 == 0."""
+    (scores depend on q - k only).  Not combinable with ``kstart``; the HIP path needs T % 64 == 0.
+    ``window`` (None / 0 = off): sliding-window attention -- query q attends to keys
+    max(kstart[b], q - window + 1) <= k <= q, the query itself counted (HF ``sliding_window``).  Composes with
+    ``kstart``, not with ``doc_bounds``.  ``window >= T`` is no window: today's path, bit for bit.  The HIP path
+    has no windowed backward for T % 64 != 0 (forward only, e.g. prefill): a gradient there is refused up front."""
     if rotated and not qkv.is_cuda:
         raise ValueError("rotated=True is a GPU-path contract (fused RoPE GEMM epilogue)")
+    if window is not None and window < 0:
+        raise ValueError(f"sliding window must be >= 1 (None / 0 = off), not {window}")
+    if window and doc_bounds is not None:
+        raise ValueError("a sliding window and doc_bounds (packed documents) cannot be combined")
+    window = int(window) if window and window < T else None
     if kstart is not None and doc_bounds is not None:
         raise ValueError("kstart (left padding) and doc_bounds (packed documents) cannot be combined")
     if doc_bounds is not None:
@@ -219,6 +249,12 @@ def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T
     if _ext.use_hip(qkv):
         if doc_bounds is not None and T % 64:
             raise ValueError(f"document-masked attention needs T % 64 == 0 on the HIP path (T = {T})")
+        if window is not None:
+            if hd not in (32, 64, 128):
+                raise ValueError(f"sliding-window attention: head_dim {hd} not in (32, 64, 128)")
+            if T % 64 and torch.is_grad_enabled() and qkv.requires_grad:
+                raise ValueError(f"sliding-window attention has no backward for T % 64 != 0 on the HIP path (T = {T}); "
+                                 "run the forward under no_grad")
         x = qkv.contiguous()
         if not inplace and x.data_ptr() == qkv.data_ptr():
             x = x.clone()  # never rotate a caller-visible tensor
@@ -227,5 +263,8 @@ def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T
             de = de.to(device=qkv.device, dtype=torch.int32).contiguous()
             return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, None, bool(rotated), ds, de)
         ks = kstart.to(device=qkv.device, dtype=torch.int32).contiguous() if kstart is not None else None
+        if window is not None:
+            return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, ks, bool(rotated), None, None, window)
         return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, ks, bool(rotated))
-    return ref.attention_block(qkv, cos, sin, B, T, nh, nkv, hd, use_sdpa=True, kstart=kstart, doc_bounds=doc_bounds)
+    return ref.attention_block(qkv, cos, sin, B, T, nh, nkv, hd, use_sdpa=True, kstart=kstart, doc_bounds=doc_bounds,
+                               window=window)

@@ -59,6 +59,9 @@ class KVCache:
         self.batch, self.s_max = int(batch), int(s_max)
         self.device, self.dtype = torch.device(device), dtype
         self.nh, self.nkv, self.hd = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        # sliding window (None = off): a decode step sees keys max(kstart, pos - window + 1) .. pos.  The cache stays
+        # static (s_max slots); only what a step reads shrinks
+        self.window = int(getattr(c, "sliding_window", None) or 0) or None
         shape = (self.batch, self.nkv, self.s_max, self.hd)
         self.k = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(c.num_hidden_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(c.num_hidden_layers)]
@@ -112,11 +115,20 @@ def _check_cache_args(qkv, cos, sin, cache: KVCache, layer: int):
     cache.check_room()
 
 
+def _check_window(window) -> Optional[int]:
+    if window is None:
+        return None
+    if int(window) < 1:
+        raise ValueError(f"decode attention: sliding window must be >= 1 (None = off), not {window}")
+    return int(window)
+
+
 def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_ml, nh: int, nkv: int, hd: int,
-                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``nd_attn_decode`` on raw tensors; every shape, dtype, contiguity and alignment the kernel relies on is
-    checked here, before the launch.  The positions live on the device and are NOT checked (``KVCache`` keeps a
-    host-side bound for that); the kernel itself ignores a position outside the cache."""
+                       out: Optional[torch.Tensor] = None, window: Optional[int] = None) -> torch.Tensor:
+    """``nd_attn_decode`` (``window``: ``nd_attn_decode_win``) on raw tensors; every shape, dtype, contiguity and
+    alignment the kernel relies on is checked here, before the launch.  The positions live on the device and are NOT
+    checked (``KVCache`` keeps a host-side bound for that); the kernel itself ignores a position outside the cache."""
+    window = _check_window(window)
     if hd not in HEAD_DIMS:
         raise ValueError(f"decode attention: head_dim {hd} not in {HEAD_DIMS}")
     if nh < 1 or nkv < 1 or nh % nkv or nh // nkv > MAX_REP:
@@ -158,6 +170,13 @@ def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_
                     ("part_o", part_o), ("part_ml", part_ml)):
         if t.data_ptr() % 16:
             raise ValueError(f"decode attention: {name} must be 16-byte aligned")
+    if window is not None:
+        _ext.check(_ext.lib().nd_attn_decode_win(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos),
+                                                 _ext.ptr(kstart), _ext.ptr(kcache), _ext.ptr(vcache), _ext.ptr(part_o),
+                                                 _ext.ptr(part_ml), _ext.ptr(out), B, nh, nkv, hd, s_max, qkv.stride(0),
+                                                 float(hd ** -0.5), min(window, 2 ** 31 - 1),
+                                                 _ext.stream_ptr(qkv.device)), "nd_attn_decode_win")
+        return out
     _ext.check(_ext.lib().nd_attn_decode(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos), _ext.ptr(kstart),
                                          _ext.ptr(kcache), _ext.ptr(vcache), _ext.ptr(part_o), _ext.ptr(part_ml),
                                          _ext.ptr(out), B, nh, nkv, hd, s_max, qkv.stride(0), float(hd ** -0.5),
@@ -165,8 +184,10 @@ def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_
     return out
 
 
-def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, nkv: int, hd: int) -> torch.Tensor:
+def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, nkv: int, hd: int,
+                           window: Optional[int] = None) -> torch.Tensor:
     """The PyTorch twin on raw tensors (any device / float dtype); same contract as ``attn_decode_launch``."""
+    window = _check_window(window)
     B, _, s_max, _ = kcache.shape
     q, k, v = qkv.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
     p = pos.long()
@@ -178,6 +199,8 @@ def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, 
     vcache[rows, :, p] = v.reshape(B, nkv, hd)
     t = torch.arange(s_max, device=qkv.device)
     lo = kstart.long().view(B, 1) if kstart is not None else torch.zeros(B, 1, dtype=torch.long, device=qkv.device)
+    if window is not None:
+        lo = torch.maximum(lo, p.view(B, 1) - window + 1)
     mask = ((t[None] >= lo) & (t[None] <= p.view(B, 1))).view(B, 1, 1, s_max)
     kk, vv = kcache, vcache
     if nkv != nh:
@@ -194,9 +217,9 @@ def attention_decode(qkv: torch.Tensor, cache: KVCache, layer: int, cos: torch.T
         if cache.part_o is None:
             cache.part_o, cache.part_ml = decode_workspace(cache.batch, cache.nh, cache.hd, cache.s_max, cache.device)
         return attn_decode_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.part_o,
-                                  cache.part_ml, cache.nh, cache.nkv, cache.hd)
+                                  cache.part_ml, cache.nh, cache.nkv, cache.hd, window=cache.window)
     return attention_decode_torch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.nh,
-                                  cache.nkv, cache.hd)
+                                  cache.nkv, cache.hd, window=cache.window)
 
 
 def cache_fill(cache: KVCache, layer: int, qkv: torch.Tensor, B: int, T: int, cos=None, sin=None,

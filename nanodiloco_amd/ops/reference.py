@@ -158,19 +158,45 @@ def doc_causal_mask(doc_start: torch.Tensor, T: int) -> torch.Tensor:
     return (causal[None] & same_doc).unsqueeze(1)
 
 
+def window_causal_mask(window: int, T: int, kstart: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """Boolean [B or 1, 1, T, T] (True = attend): causal & key inside the query's sliding window of ``window`` >= 1
+    keys, the query itself included -- ``max(kstart[b], q - window + 1) <= k <= q`` (HF's
+    ``kv_idx > q_idx - sliding_window``), composed with the left-padding key start when one is given."""
+    if window < 1:
+        raise ValueError(f"sliding window must be >= 1, not {window}")
+    device = kstart.device if kstart is not None else device
+    t = torch.arange(T, device=device)
+    m = ((t[None, :] <= t[:, None]) & (t[None, :] > t[:, None] - window))[None]
+    if kstart is not None:
+        m = m & (t.view(1, 1, T) >= kstart.view(-1, 1, 1).to(t.dtype))
+    return m.unsqueeze(1)
+
+
 def attention_block(qkv: torch.Tensor, cos, sin, B: int, T: int, nh: int, nkv: int, hd: int,
-                    use_sdpa: bool = True, kstart: torch.Tensor = None, doc_bounds=None) -> torch.Tensor:
+                    use_sdpa: bool = True, kstart: torch.Tensor = None, doc_bounds=None,
+                    window: Optional[int] = None) -> torch.Tensor:
     """qkv [B*T, (nh+2nkv)*hd] -> RoPE -> causal attention -> [B*T, nh*hd] (autograd-capable).
     ``kstart``: left-padding key start per sequence (see ``ops.attention.key_start``).
-    ``doc_bounds``: (doc_start, doc_end) of a packed window (see ``ops.attention.doc_bounds``)."""
+    ``doc_bounds``: (doc_start, doc_end) of a packed window (see ``ops.attention.doc_bounds``).
+    ``window``: sliding window (None / 0 = off; composes with ``kstart``, not with ``doc_bounds``); a window of T or
+    more keys is the whole prefix and takes the un-windowed path."""
+    if window is not None and window < 0:
+        raise ValueError(f"sliding window must be >= 1 (None / 0 = off), not {window}")
+    if window and doc_bounds is not None:
+        raise ValueError("a sliding window and doc_bounds (packed documents) cannot be combined")
+    if not window or window >= T:
+        window = None
     q, k, v = split_qkv(qkv, B, T, nh, nkv, hd)
     q = apply_rope(q, cos[:T], sin[:T])
     k = apply_rope(k, cos[:T], sin[:T])
     if kstart is not None and doc_bounds is not None:
         raise ValueError("kstart (left padding) and doc_bounds (packed documents) cannot be combined")
-    if kstart is not None or doc_bounds is not None:
-        mask = padded_causal_mask(kstart.to(qkv.device), T) if kstart is not None \
-            else doc_causal_mask(doc_bounds[0].to(qkv.device), T)
+    if kstart is not None or doc_bounds is not None or window is not None:
+        if window is not None:
+            mask = window_causal_mask(window, T, kstart.to(qkv.device) if kstart is not None else None, qkv.device)
+        else:
+            mask = padded_causal_mask(kstart.to(qkv.device), T) if kstart is not None \
+                else doc_causal_mask(doc_bounds[0].to(qkv.device), T)
         if nkv != nh:
             k = k.repeat_interleave(nh // nkv, dim=1)
             v = v.repeat_interleave(nh // nkv, dim=1)

@@ -118,6 +118,9 @@ class TrainArgs:
     tokenizer: str = "huggyllama/llama-7b"
     debug_checks: bool = False
     mask_pad_labels: bool = True
+    sliding_window: int = 0        # sliding-window attention (Mistral): every query attends to the last W keys, itself
+                                   # included, in every layer (0 = off; the same as "sliding_window": W in the model
+                                   # config).  A resumed checkpoint's config.json carries it.  docs/DESIGN.md "Sliding window"
     doc_mask: bool = False         # packed data (memmap / synthetic): attention stays inside each EOS-separated
                                    # document of a window (block-diagonal causal; ops.doc_bounds, docs/DESIGN.md)
     eval_every: int = 0            # held-out evaluation every N inner steps and once after the last (0 = off);
@@ -199,20 +202,39 @@ def check_doc_mask(doc_mask: bool, data_kind: str, seq_length: int, on_gpu: bool
         raise ValueError(f"--doc-mask on a GPU needs --seq-length to be a multiple of 64 (got {seq_length})")
 
 
-def _checkpoint_qk_norm(a: TrainArgs) -> bool:
-    """Whether the checkpoint this run resumes from holds a QK-norm model (its config.json says so): the model is
-    then built with the q_norm / k_norm weights whether or not --qk-norm is given again."""
+def check_sliding_window(window, doc_mask: bool, data_kind: str, seq_length: int, on_gpu: bool,
+                         ops_backend: str = "auto") -> None:
+    """Refuse at start-up what the windowed attention kernels cannot run.  A window and ``--doc-mask`` are refused
+    everywhere (that combination is not built).  On the HIP path with W < seq_length the backward exists for whole
+    64-key tiles only: ``--seq-length`` must be a multiple of 64, and ``--data hf`` (batches padded to multiples of 8)
+    cannot promise that.  A window of seq_length or more keys is no window and passes."""
+    if not window:
+        return
+    if window < 0:
+        raise ValueError(f"--sliding-window must be >= 1 (0 = off), got {window}")
+    if doc_mask:
+        raise ValueError("--sliding-window and --doc-mask cannot be combined")
+    if on_gpu and ops_backend != "torch" and window < seq_length:
+        if data_kind == "hf":
+            raise ValueError("--sliding-window on a GPU needs fixed windows of a multiple of 64 tokens; --data hf pads "
+                             "its batches to multiples of 8 (use --ops torch, or packed data)")
+        if seq_length % 64:
+            raise ValueError(f"--sliding-window on a GPU needs --seq-length to be a multiple of 64 (got {seq_length})")
+
+
+def _checkpoint_config(a: TrainArgs):
+    """The LlamaConfig of the checkpoint this run resumes from (None: no resume, or no config.json there)."""
     if not a.resume:
-        return False
+        return None
     import json
 
     from .utils.checkpoint import find_checkpoint
     d = find_checkpoint(a.checkpoint_dir if a.resume == "auto" else a.resume)
     path = os.path.join(d, "config.json") if d else None
     if not path or not os.path.isfile(path):
-        return False
+        return None
     with open(path) as f:
-        return LlamaConfig.from_dict(json.load(f)).qk_norm
+        return LlamaConfig.from_dict(json.load(f))
 
 
 def _resolve_data_kind(a: TrainArgs) -> str:
@@ -269,8 +291,20 @@ class Trainer:
             from .ops.tuned_gemm import enable_tuned_gemms
             enable_tuned_gemms(e.device)
         self.llama_config: LlamaConfig = resolve_llama_config(a.llama_config_file)
-        if (a.qk_norm or _checkpoint_qk_norm(a)) and not self.llama_config.qk_norm:
+        # a checkpoint's config.json says what model it holds: QK-norm weights and the sliding window come back on a
+        # resume whether or not the flags are given again
+        ck = _checkpoint_config(a)
+        if (a.qk_norm or (ck is not None and ck.qk_norm)) and not self.llama_config.qk_norm:
             self.llama_config = dataclasses.replace(self.llama_config, qk_norm=True)
+        if a.sliding_window < 0:
+            raise ValueError(f"--sliding-window must be >= 1 (0 = off), got {a.sliding_window}")
+        if ck is not None and a.sliding_window and a.sliding_window != (ck.sliding_window or 0):
+            raise ValueError(f"--sliding-window {a.sliding_window} differs from the checkpoint's sliding_window "
+                             f"({ck.sliding_window or 'off'}): a resumed run continues the model its config.json "
+                             "describes (drop the flag)")
+        window = a.sliding_window or (ck.sliding_window if ck is not None else None)
+        if window and window != self.llama_config.sliding_window:
+            self.llama_config = dataclasses.replace(self.llama_config, sliding_window=int(window))
         if str(a.per_device_batch_size).lower() == "auto":
             a.per_device_batch_size = auto_micro_batch(self.llama_config, a.seq_length, a.batch_size, e.device)
         a.per_device_batch_size = int(a.per_device_batch_size)
@@ -286,6 +320,8 @@ class Trainer:
             set_fp8_keep_fused(a.fp8_keep_fused)
         self.data_kind = _resolve_data_kind(a)
         check_doc_mask(a.doc_mask, self.data_kind, a.seq_length, e.device.type == "cuda", a.ops)
+        check_sliding_window(self.llama_config.sliding_window, a.doc_mask, self.data_kind, a.seq_length,
+                             e.device.type == "cuda", a.ops)
         self.model = LlamaForCausalLM(self.llama_config, e.device, self.compute_dtype,
                                       activation_checkpointing=a.activation_checkpointing,
                                       fp8=a.fp8 or a.dtype == "fp8", fp8_wgrad=a.fp8_wgrad,
@@ -521,6 +557,8 @@ class Trainer:
         extra = {"run_name": self.run_name}
         if self.llama_config.qk_norm:  # a checkpoint without the key holds a model without QK-norm
             extra["qk_norm"] = True
+        if self.llama_config.sliding_window:  # likewise: no key, no window
+            extra["sliding_window"] = self.llama_config.sliding_window
         save_checkpoint(self.args.checkpoint_dir, self.model, self.diloco, self.env, step, data_state=ds,
                         extra=extra)
 

@@ -8,7 +8,10 @@ half the full score matrix: fwd 2 GEMMs, bwd 5 (dkdv 4 + dq 3 recomputed = 7 exe
 of zeros (the masked kernels with nothing masked) of the same shape, interleaved in the same process: medians of
 ``--repeats`` rounds of ``--iters`` launches each, after a warm-up round.  ``--lib PATH`` adds the plain causal
 launch of another build of the kernel library (e.g. the parent commit's, ``csrc/build.py --rev``).  The document
-mode times the attention kernels alone: q|k count as already rotated, so no RoPE pass and no copy is in the figures."""
+mode times the attention kernels alone: q|k count as already rotated, so no RoPE pass and no copy is in the figures.
+
+``--window W`` (0 = off): the sliding-window launch (``ops.attention(..., window=W)``, W < T) timed the same way,
+next to the plain causal and the left-pad launch, forward and fused backward."""
 import argparse
 import os
 import statistics
@@ -34,8 +37,9 @@ def bench(fn, iters=10):
 
 
 def doc_mode(a, B, T, nh, nkv, hd):
-    """Plain causal vs left-pad (key start 0) vs document mode, forward and backward, interleaved."""
-    L = a.doc_len
+    """Plain causal vs left-pad (key start 0) vs document mode (--doc-len) or sliding window (--window), forward and
+    backward, interleaved."""
+    L = a.doc_len or T
     ld = (nh + 2 * nkv) * hd
     qkv = torch.randn(B * T, ld, device="cuda").bfloat16()
     cos, sin = rope_cache(T, hd, 10000.0, None, "cuda")
@@ -62,8 +66,11 @@ def doc_mode(a, B, T, nh, nkv, hd):
             return torch.autograd.grad(o, x, do, retain_graph=True)
         return fwd, bwd
 
-    variants = {"causal": variant({}), "leftpad ks=0": variant({"kstart": ks0}),
-                f"doc L={L}": variant({"doc_bounds": bounds})}
+    variants = {"causal": variant({}), "leftpad ks=0": variant({"kstart": ks0})}
+    if a.doc_len:
+        variants[f"doc L={L}"] = variant({"doc_bounds": bounds})
+    if a.window:
+        variants[f"window W={a.window}"] = variant({"window": a.window})
     if other is not None:
         variants["causal (--lib)"] = variant({}, other)
     outs = {k: f() for k, (f, _) in variants.items()}
@@ -77,7 +84,7 @@ def doc_mode(a, B, T, nh, nkv, hd):
                 times[k][1].append(tb)
     med = {k: (statistics.median(v[0]), statistics.median(v[1])) for k, v in times.items()}
     cf, cb = med["causal"]
-    print(f"B={B} T={T} nh={nh} nkv={nkv} hd={hd} doc_len={L}: median of {a.repeats} x {a.iters} launches")
+    print(f"B={B} T={T} nh={nh} nkv={nkv} hd={hd} doc_len={a.doc_len} window={a.window}: median of {a.repeats} x {a.iters} launches")
     print("| launch | fwd us | fwd / causal | bwd us | bwd / causal |")
     print("|---|---|---|---|---|")
     for k, (tf, tb) in med.items():
@@ -87,6 +94,7 @@ def doc_mode(a, B, T, nh, nkv, hd):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--doc-len", type=int, default=0, help="uniform documents of this many tokens (0 = off)")
+    ap.add_argument("--window", type=int, default=0, help="sliding window of this many keys, < T (0 = off)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--lib", default=None, help="another build of the kernel library: its plain causal launch is timed too")
@@ -97,9 +105,11 @@ def main():
     nkv = int(os.environ.get("NKV", nh))
     hd = int(os.environ.get("HD", 64))
     ops.set_backend("hip")
-    if a.doc_len:
-        if a.doc_len < 1 or T % a.doc_len:
+    if a.doc_len or a.window:
+        if a.doc_len and (a.doc_len < 1 or T % a.doc_len):
             raise SystemExit("--doc-len must divide T")
+        if a.window and not 1 <= a.window < T:
+            raise SystemExit("--window must lie in [1, T)")
         return doc_mode(a, B, T, nh, nkv, hd)
     ld = (nh + 2 * nkv) * hd
     qkv = torch.randn(B * T, ld, device="cuda").bfloat16()

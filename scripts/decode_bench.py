@@ -80,6 +80,37 @@ def bench_kernel(name, B, length, rounds, inner, warmup, dev):
     return r
 
 
+def bench_window(name, B, length, window, rounds, inner, warmup, dev):
+    """``nd_attn_decode_win`` against ``nd_attn_decode`` on the same cache at position ``length - 1``, interleaved."""
+    nh, nkv, hd = SHAPES[name]
+    s_max = max(S_MAX, length)
+    g = torch.Generator(device=dev).manual_seed(B * 7 + length)
+    kc = torch.randn(B, nkv, s_max, hd, device=dev, generator=g).bfloat16()
+    vc = torch.randn(B, nkv, s_max, hd, device=dev, generator=g).bfloat16()
+    qkv = torch.randn(B, (nh + 2 * nkv) * hd, device=dev, generator=g).bfloat16()
+    cos, sin = rope_cache(s_max, hd, 10000.0, None, dev)
+    pos = torch.full((B,), length - 1, dtype=torch.int32, device=dev)
+    ks = torch.zeros(B, dtype=torch.int32, device=dev)
+    part_o, part_ml = decode.decode_workspace(B, nh, hd, s_max, dev)
+    out = torch.empty(B, nh * hd, dtype=torch.bfloat16, device=dev)
+    fns = {"full": lambda: decode.attn_decode_launch(qkv, cos, sin, pos, ks, kc, vc, part_o, part_ml, nh, nkv, hd, out=out),
+           "window": lambda: decode.attn_decode_launch(qkv, cos, sin, pos, ks, kc, vc, part_o, part_ml, nh, nkv, hd,
+                                                       out=out, window=window)}
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            ms[k].append(timed(f, inner)[0])
+    r = {"shape": name, "B": B, "len": length, "window": window, "s_max": s_max}
+    for k, v in ms.items():
+        r[k + "_us_median"], r[k + "_us_min"] = 1e3 * statistics.median(v), 1e3 * min(v)
+    r["window_over_full"] = r["window_us_median"] / r["full_us_median"]
+    return r
+
+
 def bench_e2e(B, prompt, new, rounds, dev):
     from nanodiloco_amd.config import resolve_llama_config
     from nanodiloco_amd.models import LlamaForCausalLM
@@ -134,12 +165,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--e2e-rounds", type=int, default=3)
     ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--window", type=int, default=0,
+                    help="time the sliding-window decode step (this many keys) against the full one at --len, and stop")
+    ap.add_argument("--len", type=int, default=4096, help="with --window: keys in the cache (pos = len - 1)")
     ap.add_argument("--out", default=None, help="also write the tables (markdown) here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs a GPU: a CPU timing says nothing about the kernels")
     ops.set_backend("hip")
     dev = torch.device("cuda")
+    if a.window:
+        for name in SHAPES:
+            for B in (1, 8, 64):
+                print(json.dumps(bench_window(name, B, a.len, a.window, a.rounds, a.inner, a.warmup, dev)), flush=True)
+        return
     kern, e2e = [], []
     for name in SHAPES:
         for B in (1, 8, 64):
