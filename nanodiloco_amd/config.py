@@ -100,6 +100,9 @@ class LlamaConfig:
     # sliding-window attention (Mistral): every layer's query q sees keys q - W + 1 .. q; None / 0 = off
     # (docs/DESIGN.md "Sliding window")
     sliding_window: Optional[int] = None
+    # final-logit soft-capping (Gemma 2's key): the model's logits are C * tanh(logits / C); None / 0 = off
+    # (docs/DESIGN.md "Logit soft-capping")
+    final_logit_softcapping: Optional[float] = None
     architectures: Optional[list] = None
     extra: Dict[str, Any] = dataclasses.field(default_factory=dict)
 
@@ -110,6 +113,9 @@ class LlamaConfig:
             self.head_dim = self.hidden_size // self.num_attention_heads
         if self.sliding_window == 0:
             self.sliding_window = None
+        cap = self.final_logit_softcapping
+        if cap is not None and not isinstance(cap, (bool, str)) and cap == 0:
+            self.final_logit_softcapping = None
         # transformers>=5 stores rope_theta inside rope_parameters; accept both spellings.
         rp = self.extra.get("rope_parameters")
         if isinstance(rp, dict) and "rope_theta" in rp:
@@ -153,6 +159,8 @@ class LlamaConfig:
             del d["qk_norm"]  # off: the dict is what it always was
         if not self.sliding_window:
             del d["sliding_window"]  # likewise
+        if not self.final_logit_softcapping:
+            del d["final_logit_softcapping"]  # likewise
         if d.get("architectures") is None:
             d["architectures"] = ["LlamaForCausalLM"]
         return d
@@ -180,6 +188,10 @@ class LlamaConfig:
         if self.sliding_window is not None and (isinstance(self.sliding_window, bool)
                                                 or not isinstance(self.sliding_window, int) or self.sliding_window < 1):
             raise ValueError(f"sliding_window must be an integer >= 1 (0 / null = off), got {self.sliding_window!r}")
+        cap = self.final_logit_softcapping
+        if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, float))
+                                or not 0.0 < float(cap) < float("inf")):  # NaN fails both comparisons
+            raise ValueError(f"final_logit_softcapping must be a finite number > 0 (0 / null = off), got {cap!r}")
         if self.rope_scaling not in (None, {}) and self.rope_scaling.get("rope_type", self.rope_scaling.get("type")) not in (
             "default", "linear", "llama3"):
             raise ValueError(f"unsupported rope_scaling {self.rope_scaling}")

@@ -16,9 +16,19 @@
 // and lse^2 goes to an accumulator of its own (z_sum, or one store per row into row_z): the cross-entropy sum
 // never contains the z term.  Z = the kernel was instantiated with a ZArgs parameter; without one every
 // `if constexpr (Z)` is compiled out and the kernel is what it was.
+//
+// Logit soft-capping (CAP = true instantiations, nd_ce_cap_fwd_bwd / nd_ce_cap_fwd_bwd_q8; softcap.h): the model's
+// logits are y = C tanh(x / C) of the stored x, formed in fp32 and never rounded back, so with t = tanh(x / C)
+//   lse = logsumexp(y), loss_row = lse - y[target], x <- (exp(y - lse) * g - [j == target]) * scale * (1 - t^2)
+// (g = 1 without z-loss; lse_out and the z term use this lse).  tanh is monotone: the max pass runs on the stored
+// values and the row's maximum is capped once.  The row is held as stored and t is formed again in the sum pass and in
+// the gradient pass.  CAP = a CapArgs parameter follows the ZArgs, if any; without one every `if constexpr (CAP)` is
+// compiled out.
 #include "common.h"
+#include "softcap.h"
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 using namespace nd;
 
@@ -29,8 +39,13 @@ struct ZArgs {
   float* row_z;   // per row: lse^2 (0 where the target is ignored); deterministic mode, no float atomic
 };
 // The kernels take it as a trailing parameter pack: empty (the plain kernels, whose signature and code stay as they
-// were) or one ZArgs (Z = true).
+// were), one ZArgs (Z = true), one CapArgs (CAP = true) or a ZArgs and a CapArgs, in this order.
 __device__ __forceinline__ const ZArgs& zarg(const ZArgs& z) { return z; }
+__device__ __forceinline__ const ZArgs& zarg(const ZArgs& z, const CapArgs&) { return z; }
+__device__ __forceinline__ const CapArgs& caparg(const CapArgs& c) { return c; }
+__device__ __forceinline__ const CapArgs& caparg(const ZArgs&, const CapArgs& c) { return c; }
+template <class T, class... A>
+constexpr bool has_arg = (std::is_same_v<T, A> || ...);
 
 // the row's z term, by thread 0 after the cross-entropy has gone out
 __device__ __forceinline__ void z_commit(const ZArgs& z, int64_t row, bool valid, float lse) {
@@ -56,7 +71,7 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
                                                      float* __restrict__ loss_sum, const float* __restrict__ scale_p,
                                                      int V, int ignore, float* __restrict__ lse_out,
                                                      float* __restrict__ row_loss, ZA... z) {
-  constexpr bool Z = sizeof...(ZA) > 0;
+  constexpr bool Z = has_arg<ZArgs, ZA...>, CAP = has_arg<CapArgs, ZA...>;
   __shared__ float red[8];
   const int64_t row = blockIdx.x;
   const int64_t base = row * (int64_t)V;
@@ -74,13 +89,22 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
     }
   }
   m = block_max<256>(m, red);
+  float cap = 0.f, cinv = 0.f;
+  if constexpr (CAP) {
+    cap = caparg(z...).cap;
+    cinv = caparg(z...).inv;
+    m = cap * cap_tanh(m * cinv);  // the maximum of the capped row
+  }
   float s = 0.f;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     const int col = (c * 256 + threadIdx.x) * 8;
     if (col < V) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s += __expf(x[c][j] - m);
+      for (int j = 0; j < 8; ++j) {
+        if constexpr (CAP) s += __expf(fmaf(cap, cap_tanh(x[c][j] * cinv), -m));
+        else s += __expf(x[c][j] - m);
+      }
     }
   }
   __syncthreads();
@@ -98,9 +122,16 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(void* __restrict__ logits, 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool hit = (int64_t)(col + j) == tgt;
-        if (hit) picked = x[c][j];
-        if constexpr (Z) o[j] = fmaf(__expf(x[c][j] - lse), scg, hit ? -sc : 0.f);
-        else o[j] = (__expf(x[c][j] - lse) - (hit ? 1.f : 0.f)) * sc;
+        if constexpr (CAP) {
+          float d;
+          const float y = cap * cap_tanh(x[c][j] * cinv, d);
+          if (hit) picked = y;
+          o[j] = fmaf(__expf(y - lse), scg, hit ? -sc : 0.f) * d;
+        } else {
+          if (hit) picked = x[c][j];
+          if constexpr (Z) o[j] = fmaf(__expf(x[c][j] - lse), scg, hit ? -sc : 0.f);
+          else o[j] = (__expf(x[c][j] - lse) - (hit ? 1.f : 0.f)) * sc;
+        }
       }
       Vec8<DT>::store(logits, base + col, o);
     }
@@ -131,7 +162,7 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
                                                       float* __restrict__ loss_sum, const float* __restrict__ scale_p,
                                                       int V, int ignore, float* __restrict__ lse_out,
                                                      float* __restrict__ row_loss, Fp8Out q8, ZA... z) {
-  constexpr bool Z = sizeof...(ZA) > 0;
+  constexpr bool Z = has_arg<ZArgs, ZA...>, CAP = has_arg<CapArgs, ZA...>;
   constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
   __shared__ float red[8];
   const int64_t row = blockIdx.x;
@@ -151,7 +182,16 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
     }
   }
   m = block_max<256>(m, red);
-  const float m2 = m * L2E;
+  float cap = 0.f, cap2 = 0.f, cinv = 0.f;  // cap2: C log2(e), the capped logit in the log2 domain is t * cap2
+  if constexpr (CAP) {
+    cap = caparg(z...).cap;
+    cap2 = cap * L2E;
+    cinv = caparg(z...).inv;
+  }
+  float m2_;
+  if constexpr (CAP) m2_ = cap2 * cap_tanh(m * cinv);  // the capped row's maximum: the same products as its element
+  else m2_ = m * L2E;
+  const float m2 = m2_;
   // opaque to the optimiser: stops it from keeping the unpacked fp32 copies alive across passes
 #pragma unroll
   for (int c = 0; c < CH; ++c) asm volatile("" : "+v"(x[c].x), "+v"(x[c].y), "+v"(x[c].z), "+v"(x[c].w));
@@ -162,8 +202,13 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
     if (col < V) {
       const uint32_t u[4] = {x[c].x, x[c].y, x[c].z, x[c].w};
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        s += __builtin_amdgcn_exp2f(fmaf(lo_bf(u[j]), L2E, -m2)) + __builtin_amdgcn_exp2f(fmaf(hi_bf(u[j]), L2E, -m2));
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (CAP)
+          s += __builtin_amdgcn_exp2f(fmaf(cap_tanh(lo_bf(u[j]) * cinv), cap2, -m2)) +
+               __builtin_amdgcn_exp2f(fmaf(cap_tanh(hi_bf(u[j]) * cinv), cap2, -m2));
+        else
+          s += __builtin_amdgcn_exp2f(fmaf(lo_bf(u[j]), L2E, -m2)) + __builtin_amdgcn_exp2f(fmaf(hi_bf(u[j]), L2E, -m2));
+      }
     }
   }
   __syncthreads();
@@ -185,8 +230,14 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
       float o[8];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        o[2 * j] = __builtin_amdgcn_exp2f(fmaf(lo_bf(u[j]), L2E, -lse2)) * scg;
-        o[2 * j + 1] = __builtin_amdgcn_exp2f(fmaf(hi_bf(u[j]), L2E, -lse2)) * scg;
+        if constexpr (CAP) {
+          float d0, d1;  // 1 - t^2
+          o[2 * j] = __builtin_amdgcn_exp2f(fmaf(cap_tanh(lo_bf(u[j]) * cinv, d0), cap2, -lse2)) * scg * d0;
+          o[2 * j + 1] = __builtin_amdgcn_exp2f(fmaf(cap_tanh(hi_bf(u[j]) * cinv, d1), cap2, -lse2)) * scg * d1;
+        } else {
+          o[2 * j] = __builtin_amdgcn_exp2f(fmaf(lo_bf(u[j]), L2E, -lse2)) * scg;
+          o[2 * j + 1] = __builtin_amdgcn_exp2f(fmaf(hi_bf(u[j]), L2E, -lse2)) * scg;
+        }
       }
       const unsigned d = (unsigned)(tgt - col);
       if (d < 8u) {  // this thread owns the target column
@@ -194,7 +245,13 @@ __global__ void __launch_bounds__(256) ce_bf16_kernel(bf16_t* __restrict__ logit
         for (int j = 0; j < 8; ++j)
           if ((unsigned)j == d) {
             picked = (j & 1) ? hi_bf(u[j >> 1]) : lo_bf(u[j >> 1]);
-            o[j] -= sc;
+            if constexpr (CAP) {  // the column's own 1 - t^2 once more: s (p g - 1) (1 - t^2)
+              float dd;
+              picked = cap * cap_tanh(picked * cinv, dd);
+              o[j] = fmaf(-sc, dd, o[j]);
+            } else {
+              o[j] -= sc;
+            }
           }
       }
       uint4 w;
@@ -230,7 +287,7 @@ __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logi
                                                          float* __restrict__ loss_sum, const float* __restrict__ scale_p,
                                                          int V, int ignore, float* __restrict__ lse_out,
                                                      float* __restrict__ row_loss, ZA... z) {
-  constexpr bool Z = sizeof...(ZA) > 0;
+  constexpr bool Z = has_arg<ZArgs, ZA...>, CAP = has_arg<CapArgs, ZA...>;
   __shared__ float red[8];
   const int64_t row = blockIdx.x;
   const int64_t base = row * (int64_t)V;
@@ -240,9 +297,15 @@ __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logi
     if (DT == BF16) return bf2f(reinterpret_cast<const bf16_t*>(logits)[base + j]);
     return reinterpret_cast<const float*>(logits)[base + j];
   };
+  float cap = 0.f, cinv = 0.f;
+  if constexpr (CAP) {
+    cap = caparg(z...).cap;
+    cinv = caparg(z...).inv;
+  }
   float m = -INFINITY, s = 0.f;
   for (int j = threadIdx.x; j < V; j += 256) {
-    const float v = ld(j);
+    float v = ld(j);
+    if constexpr (CAP) v = cap * cap_tanh(v * cinv);  // the online (max, sum) of the capped row
     const float nm = fmaxf(m, v);
     s = s * __expf(m - nm) + __expf(v - nm);
     m = nm;
@@ -257,11 +320,14 @@ __global__ void __launch_bounds__(256) ce_generic_kernel(void* __restrict__ logi
   if constexpr (Z) scg = valid ? sc * fmaf(2.f * zarg(z...).coef, lse, 1.f) : 0.f;
   float picked = 0.f;
   for (int j = threadIdx.x; j < V; j += 256) {
-    const float v = ld(j);
+    float v = ld(j);
+    [[maybe_unused]] float d;
+    if constexpr (CAP) v = cap * cap_tanh(v * cinv, d);
     const bool hit = (int64_t)j == tgt;
     if (hit) picked = v;
     float o;
-    if constexpr (Z) o = fmaf(__expf(v - lse), scg, hit ? -sc : 0.f);
+    if constexpr (CAP) o = fmaf(__expf(v - lse), scg, hit ? -sc : 0.f) * d;
+    else if constexpr (Z) o = fmaf(__expf(v - lse), scg, hit ? -sc : 0.f);
     else o = (__expf(v - lse) - (hit ? 1.f : 0.f)) * sc;
     if (DT == BF16) reinterpret_cast<bf16_t*>(logits)[base + j] = f2bf(o);
     else reinterpret_cast<float*>(logits)[base + j] = o;
@@ -382,5 +448,78 @@ ND_API int nd_ce_z_fwd_bwd_q8(void* logits, int dt, const int64_t* targets, floa
   else
     hipLaunchKernelGGL((ce_bf16_kernel<16, 1, ZArgs>), g, b, 0, s, (bf16_t*)logits, targets, loss_sum, scale, V, ignore, lse_out,
                        row_loss, q8, z);
+  ND_LAUNCH_CHECK();
+}
+
+// Capped forms (logit soft-capping, C = cap): one pair of entry points for the objective with and without z-loss.
+// z-loss is on when z_sum or row_z is given (then z_coef as nd_ce_z_fwd_bwd takes it); with neither, z_coef must be 0.
+// A cap that is <= 0, NaN or infinite is refused before any launch.  Dispatch borders and, for _q8, the acceptance
+// rule are those of the entry points above.
+template <class... A>
+static void ce_cap_dispatch(void* logits, int dt, const int64_t* targets, float* loss_sum, const float* scale, int64_t n,
+                            int V, int ignore, float* lse_out, float* row_loss, hipStream_t s, A... a) {
+  dim3 g((unsigned)n), b(256);
+  if (V % 8 == 0 && V <= 256 * 8 * 16) {
+    if (V <= 256 * 8 * 4) {
+      if (dt == BF16) hipLaunchKernelGGL((ce_reg_kernel<BF16, 4, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, a...);
+      else hipLaunchKernelGGL((ce_reg_kernel<F32, 4, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, a...);
+    } else {
+      if (dt == BF16 && !g_ce_reg)
+        hipLaunchKernelGGL((ce_bf16_kernel<16, -1, A...>), g, b, 0, s, (bf16_t*)logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss,
+                           Fp8Out{nullptr, nullptr, nullptr, 1, 0}, a...);
+      else if (dt == BF16) hipLaunchKernelGGL((ce_reg_kernel<BF16, 16, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, a...);
+      else hipLaunchKernelGGL((ce_reg_kernel<F32, 16, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, a...);
+    }
+  } else {
+    if (dt == BF16) hipLaunchKernelGGL((ce_generic_kernel<BF16, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, a...);
+    else hipLaunchKernelGGL((ce_generic_kernel<F32, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out, row_loss, a...);
+  }
+}
+
+static bool cap_call_ok(const float* z_sum, const float* row_z, float z_coef, float cap) {
+  if (!cap_ok(cap)) return false;
+  return (z_sum || row_z) ? z_args_ok(z_sum, row_z, z_coef) : z_coef == 0.f;
+}
+
+ND_API int nd_ce_cap_fwd_bwd(void* logits, int dt, const int64_t* targets, float* loss_sum, float* z_sum,
+                             const float* scale, int64_t n, int V, int ignore, float* lse_out, float* row_loss,
+                             float* row_z, float z_coef, float cap, hipStream_t s) {
+  if (!cap_call_ok(z_sum, row_z, z_coef, cap)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (z_sum || row_z)
+    ce_cap_dispatch(logits, dt, targets, loss_sum, scale, n, V, ignore, lse_out, row_loss, s, ZArgs{z_coef, z_sum, row_z},
+                    cap_args(cap));
+  else
+    ce_cap_dispatch(logits, dt, targets, loss_sum, scale, n, V, ignore, lse_out, row_loss, s, cap_args(cap));
+  ND_LAUNCH_CHECK();
+}
+
+template <class... A>
+static void ce_cap_dispatch_q8(bf16_t* logits, const int64_t* targets, float* loss_sum, const float* scale, int64_t n, int V,
+                               int ignore, float* lse_out, float* row_loss, const Fp8Out& q8, hipStream_t s, A... a) {
+  dim3 g((unsigned)n), b(256);
+  if (q8.fmt == 0)
+    hipLaunchKernelGGL((ce_bf16_kernel<16, 0, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out,
+                       row_loss, q8, a...);
+  else
+    hipLaunchKernelGGL((ce_bf16_kernel<16, 1, A...>), g, b, 0, s, logits, targets, loss_sum, scale, V, ignore, lse_out,
+                       row_loss, q8, a...);
+}
+
+ND_API int nd_ce_cap_fwd_bwd_q8(void* logits, int dt, const int64_t* targets, float* loss_sum, float* z_sum,
+                                const float* scale, int64_t n, int V, int ignore, float* lse_out, float* row_loss,
+                                float* row_z, float z_coef, float cap, void* q, const float* qscale, float* amax,
+                                int parts, int fmt, hipStream_t s) {
+  if (!cap_call_ok(z_sum, row_z, z_coef, cap)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (dt != BF16 || V % 8 != 0 || V <= 256 * 8 * 4 || V > 256 * 8 * 16 || g_ce_reg || !q || !qscale || !amax ||
+      parts < 1 || (fmt != 0 && fmt != 1))
+    return (int)hipErrorInvalidValue;
+  const Fp8Out q8{(uint8_t*)q, qscale, amax, parts, fmt};
+  if (z_sum || row_z)
+    ce_cap_dispatch_q8((bf16_t*)logits, targets, loss_sum, scale, n, V, ignore, lse_out, row_loss, q8, s,
+                       ZArgs{z_coef, z_sum, row_z}, cap_args(cap));
+  else
+    ce_cap_dispatch_q8((bf16_t*)logits, targets, loss_sum, scale, n, V, ignore, lse_out, row_loss, q8, s, cap_args(cap));
   ND_LAUNCH_CHECK();
 }

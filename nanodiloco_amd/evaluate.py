@@ -6,7 +6,8 @@
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``, the HF-loadable fp32 master weights) -- no optimizer, no DiLoCo state -- and the model config
-comes from ``--llama-config-file`` or the checkpoint's ``config.json``.  With the data settings of the training run
+comes from ``--llama-config-file`` or the checkpoint's ``config.json`` (with ``final_logit_softcapping`` in it the
+loss is that of the soft-capped logits, as in training).  With the data settings of the training run
 (rank 0 of world 1) it prints, as one JSON line, the ``eval_loss`` that run logged for the same weights.
 """
 from __future__ import annotations

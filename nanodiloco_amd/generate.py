@@ -7,7 +7,8 @@
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``), the config comes from ``--llama-config-file`` or the checkpoint's ``config.json`` -- as
-``nanodiloco_amd.evaluate`` does.  ``--prompt-ids`` may be given several times; ``--prompt-file`` holds one JSON list
+``nanodiloco_amd.evaluate`` does (QK-norm, a sliding window and ``final_logit_softcapping`` come with it: the logits
+every token is drawn from are the capped ones).  ``--prompt-ids`` may be given several times; ``--prompt-file`` holds one JSON list
 of ids per line.  The prompts form one left-padded batch.  Output: one JSON line per prompt (``prompt_ids``,
 ``token_ids``: prompt + continuation, ``new_tokens``; with a tokenizer also ``text``), then one line with
 ``prefill_s``, ``decode_s`` and ``decode_tokens_per_s``.  ``--tokenizer PATH`` (optional) encodes ``--prompt`` and decodes

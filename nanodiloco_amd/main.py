@@ -57,6 +57,8 @@ def parse_args(argv: Optional[List[str]] = None) -> TrainArgs:
         parser.error("--doc-mask is for packed data (--data memmap | synthetic), not --data hf")
     if ns.sliding_window < 0:
         parser.error("--sliding-window must be >= 1 (0 = off)")
+    if not 0.0 <= ns.logit_softcap < float("inf"):  # NaN fails both comparisons
+        parser.error("--logit-softcap must be a finite cap > 0 (0 = off)")
     if ns.sliding_window and ns.doc_mask:
         parser.error("--sliding-window and --doc-mask cannot be combined")
     return TrainArgs(**vars(ns))

@@ -14,7 +14,8 @@ weights load here.  The compute graph is our own:
     y,h = add_rmsnorm(h, o @ Wo^T, w_post)  residual add fused into the norm
     act = swiglu(y @ [Wgate|Wup]^T)         ONE GEMM, SwiGLU in its epilogue (SwiGLU backward in the
     y,h = add_rmsnorm(h, act @ Wdown^T, ..) down projection's dgrad epilogue)
-  loss = lm_head_ce(y, W_lm, targets)       fused chunked GEMM + CE (+ its backward)
+  loss = lm_head_ce(y, W_lm, targets)       fused chunked GEMM + CE (+ its backward); config.final_logit_softcapping
+                                            = C: on C * tanh(logits / C), as every logit the model hands out
 
 Weight gradients are written straight into ``store.grad`` by the ops' backward (and, for the
 lm head, during the forward).  ``layer_hook(i)`` is called from the backward as soon as every
@@ -81,6 +82,9 @@ class LlamaForCausalLM:
         # z-loss coefficient of the training objective (--z-loss; ops/cross_entropy.py): 0.0 = off.  A hyperparameter,
         # not state; evaluation (loss_stats) ignores it
         self.z_loss = 0.0
+        # final-logit soft cap C (config.final_logit_softcapping; 0.0 = off): a property of the model, so it acts
+        # wherever a logit is produced -- training loss, loss_stats, forward().logits, prefill and decode_step
+        self.softcap = float(config.final_logit_softcapping or 0.0)
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype
         # residual stream: fp32 (default, the autocast recipe) or bf16 (Megatron's default; ops/norm.py)
@@ -250,11 +254,12 @@ class LlamaForCausalLM:
         if labels is not None or targets is not None:
             if targets is None:
                 targets = ops.reference.shift_labels(labels, ops.IGNORE_INDEX)
-            out.loss, out.ce_loss, out.z_loss = self.proj.lm_head_ce(y, targets.reshape(-1), loss_scale, self.z_loss)
+            out.loss, out.ce_loss, out.z_loss = self.proj.lm_head_ce(y, targets.reshape(-1), loss_scale, self.z_loss,
+                                                                     self.softcap)
         if return_logits or (labels is None and targets is None):
             with torch.no_grad():
                 B, T = input_ids.shape
-                out.logits = ops.mm_nt(y.detach(), self._w(self._lm_name())).float().view(B, T, -1)
+                out.logits = self._capped(ops.mm_nt(y.detach(), self._w(self._lm_name())).float()).view(B, T, -1)
         return out
 
     @torch.no_grad()
@@ -274,13 +279,18 @@ class LlamaForCausalLM:
         with self._inference():
             y = self.hidden_states(input_ids, attention_mask)
             targets = ops.reference.shift_labels(labels, ops.IGNORE_INDEX).reshape(-1)
-            row_loss, row_hit = ops.lm_head_loss(y, self._w(self._lm_name()), targets)
+            row_loss, row_hit = ops.lm_head_loss(y, self._w(self._lm_name()), targets, softcap=self.softcap)
         return torch.stack([row_loss.sum(dtype=torch.float64), (targets != ops.IGNORE_INDEX).sum().double(),
                             row_hit.sum().double()])
 
     # ------------------------------------------------------------------ generation
     def _lm_name(self) -> str:
         return "lm_head.weight" if not self.config.tie_word_embeddings else "model.embed_tokens.weight"
+
+    def _capped(self, logits: torch.Tensor) -> torch.Tensor:
+        """The fp32 logits of a projection as the model hands them out: soft-capped in place when the config says so
+        (one HIP kernel on the HIP path, static shapes: capturable)."""
+        return ops.logit_softcap(logits, self.softcap) if self.softcap else logits
 
     @contextlib.contextmanager
     def _inference(self):
@@ -317,7 +327,7 @@ class LlamaForCausalLM:
             else:
                 cache.kstart.zero_()
             last = y.view(B, T, -1)[:, -1].contiguous()
-            return ops.mm_nt(last, self._w(self._lm_name())).float()
+            return self._capped(ops.mm_nt(last, self._w(self._lm_name())).float())
 
     def _decode_device(self, tokens: torch.Tensor, cache) -> torch.Tensor:
         """The device work of one decode step (static shapes, no host sync: HIP-graph capturable), ``pos += 1``
@@ -342,7 +352,7 @@ class LlamaForCausalLM:
             m = ops.mm_nt(ops.swiglu(gu), self._w(p + "mlp.down_proj.weight"))
             nxt = f"model.layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "model.norm.weight"
             y, h = ops.add_rmsnorm(h, m, self._m(nxt), None, eps, cdt)
-        logits = ops.mm_nt(y, self._w(self._lm_name())).float()
+        logits = self._capped(ops.mm_nt(y, self._w(self._lm_name())).float())
         cache.pos += 1
         return logits
 

@@ -98,9 +98,10 @@ class Bf16Projections:
             return mlp_fused(y, w_gu, gw_gu, wt_gu, w_dn, gw_dn, wt_dn)
         return linear(swiglu(linear(y, w_gu, gw_gu, wt_gu)), w_dn, gw_dn, wt_dn)
 
-    def lm_head_ce(self, y, targets, loss_scale, z_loss=0.0):  # -> ops.LMHeadLoss (objective, its CE and z parts)
+    def lm_head_ce(self, y, targets, loss_scale, z_loss=0.0, softcap=0.0):  # -> ops.LMHeadLoss (objective, CE, z part)
         w, gw = self.lm_w()
-        return lm_head_ce_parts(y, w, gw, targets, loss_scale, wt=self._wt("lm_head", w), z_loss=z_loss)
+        return lm_head_ce_parts(y, w, gw, targets, loss_scale, wt=self._wt("lm_head", w), z_loss=z_loss,
+                                softcap=softcap)
 
 
 class Fp8Projections:
@@ -174,10 +175,10 @@ class Fp8Projections:
         act = swiglu(gu, q8=q_down, q8_bwd=self.dy_target(kgu))
         return self.lin(kdn, act, w_dn, gw_dn, version, q_down.out if q_down is not None else None)
 
-    def lm_head_ce(self, y, targets, loss_scale, z_loss=0.0):
+    def lm_head_ce(self, y, targets, loss_scale, z_loss=0.0, softcap=0.0):
         y8, self._lm_q = self.lm_y8, None
         if not self._quantises(LM_KEY):
-            return self.bf16.lm_head_ce(y, targets, loss_scale, z_loss)
+            return self.bf16.lm_head_ce(y, targets, loss_scale, z_loss, softcap)
         w, gw = self.bf16.lm_w()
         return lm_head_ce_parts(y, w, gw, targets, loss_scale, f8=self.lin, version=self.m().store.version, y8=y8,
-                                z_loss=z_loss)
+                                z_loss=z_loss, softcap=softcap)

@@ -12,7 +12,7 @@ from .swiglu import swiglu
 from .attention import attention, rope_cache, set_attn_fused_stats, key_start, check_padding, doc_bounds, \
     check_doc_bounds
 from .decode import KVCache, attention_decode, cache_fill, decode_split
-from .cross_entropy import lm_head_ce, lm_head_ce_parts, lm_head_loss, LMHeadLoss, IGNORE_INDEX
+from .cross_entropy import lm_head_ce, lm_head_ce_parts, lm_head_loss, logit_softcap, LMHeadLoss, IGNORE_INDEX
 from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov, frag_pseudograd, frag_outer_mix, \
     SpanTable
 from .muon import ns_gram, ns_poly, ns_update, ns_iterate, newton_schulz, muon_step, adamw_step_spans, \
@@ -29,7 +29,7 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "set_dgrad_transposed", "dgrad_transposed_enabled", "transpose_into",
            "rmsnorm", "rmsnorm_res", "add_rmsnorm", "qk_norm", "qk_norm_rope", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
            "KVCache", "attention_decode", "cache_fill", "decode_split",
-           "lm_head_ce", "lm_head_ce_parts", "LMHeadLoss", "lm_head_loss",
+           "lm_head_ce", "lm_head_ce_parts", "LMHeadLoss", "lm_head_loss", "logit_softcap",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
            "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "pseudograd_topk", "outer_nesterov_topk",
            "topk_slot_bytes", "densify", "LowRankPlan", "lowrank_project", "lowrank_orthonormalize",

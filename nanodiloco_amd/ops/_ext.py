@@ -175,8 +175,14 @@ def _declare(L: ctypes.CDLL):
         # the same with z-loss: (+ z_sum after loss_sum, row_z and z_coef after row_loss)
         "nd_ce_z_fwd_bwd": [P, I, P, P, P, P, L64, I, I, P, P, P, F, P],
         "nd_ce_z_fwd_bwd_q8": [P, I, P, P, P, P, L64, I, I, P, P, P, F, P, P, P, I, I, P],
+        # logit soft-capping: the z signatures (z_sum = row_z = 0, z_coef = 0: no z-loss) + cap after z_coef
+        "nd_ce_cap_fwd_bwd": [P, I, P, P, P, P, L64, I, I, P, P, P, F, F, P],
+        "nd_ce_cap_fwd_bwd_q8": [P, I, P, P, P, P, L64, I, I, P, P, P, F, F, P, P, P, I, I, P],
         # loss only (evaluation, csrc/ce_loss.hip): const logits, per-row loss / lse / top-1 hit
         "nd_ce_loss": [P, I, P, L64, I, I, P, P, P, P],
+        "nd_ce_loss_cap": [P, I, P, L64, I, I, P, P, P, F, P],
+        # in place x <- cap * tanh(x / cap) over a flat bf16 / fp32 buffer
+        "nd_logit_softcap": [P, I, L64, F, P],
         # embedding
         "nd_embedding_fwd": [P, P, P, I, L64, I, I, P],
         "nd_embedding_bwd": [P, P, I, P, L64, I, I, P],

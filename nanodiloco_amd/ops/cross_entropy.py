@@ -24,6 +24,13 @@ the objective, cross-entropy + weighted z term; ``lm_head_ce_parts`` also gives 
 device scalars (no host sync).  With ``z_loss == 0.0`` the entry points called, the launches and every bit are
 those of the z-free path.
 
+Logit soft-capping (``softcap`` = C > 0, --logit-softcap; docs/DESIGN.md "Logit soft-capping"): the model's logits are
+``C * tanh(logits / C)``.  For the same reason the cap lives in the CE kernels: ``nd_ce_cap_fwd_bwd`` /
+``nd_ce_cap_fwd_bwd_q8`` are step 2 on the capped logits, formed in fp32 from the stored ones, with
+``dlogits = s * (softmax * g - onehot) * (1 - tanh^2)`` (g = 1 without z-loss), and ``nd_ce_loss_cap`` is the loss-only
+kernel on them.  With ``softcap == 0.0`` the entry points called, the launches and every bit are those of the cap-free
+path.  ``logit_softcap`` caps a logits tensor the model hands out, in place.
+
 fp8 (``f8`` = the model's ``Fp8Linears``, BASELINE config 5): the three GEMMs run on the own fp8 kernels --
 logits = e4m3 y8 . W8^T, the CE kernel writes the dlogits straight as e5m2 (delayed scaling, slot "x.lm";
 ``nd_ce_fwd_bwd_q8``, bitwise the bf16 dlogits + separate cast that the first step, which has no scale yet,
@@ -85,7 +92,8 @@ class LMHeadCEFn(torch.autograd.Function):
     not differentiable."""
 
     @staticmethod
-    def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None, version=0, y8=None, z_loss=0.0):
+    def forward(ctx, y, w, gw, targets, loss_scale, chunk_rows, wt, f8=None, version=0, y8=None, z_loss=0.0,
+                softcap=0.0):
         n, d = y.shape
         V = w.shape[0]
         targets = targets.reshape(-1)
@@ -113,7 +121,9 @@ class LMHeadCEFn(torch.autograd.Function):
                 rows = torch.empty(e - s, dtype=torch.float32, device=y.device) if det else None
                 dl8 = None
                 t8 = r.target(kdy, E5M2) if q is not None else None
-                if z_loss:
+                if softcap:
+                    dl8 = _ce_cap_launch(logits, tc, loss_sum, z_sum, scale, rows, z_loss, softcap, t8)
+                elif z_loss:
                     dl8 = _ce_z_launch(logits, tc, loss_sum, z_sum, scale, rows, z_loss, t8)
                 elif t8 is not None:
                     # fp8: the CE kernel writes the e5m2 dlogits itself (no bf16 dlogits, no separate cast)
@@ -126,7 +136,7 @@ class LMHeadCEFn(torch.autograd.Function):
                         dl8 = q8
                     elif rc != _HIP_INVALID_VALUE:  # invalid value = shape not taken: cast separately below
                         _ext.check(rc, "nd_ce_fwd_bwd_q8")
-                if dl8 is None and not z_loss:
+                if dl8 is None and not z_loss and not softcap:
                     _ext.check(_ext.lib().nd_ce_fwd_bwd(_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc),
                                                         _ext.ptr(loss_sum), _ext.ptr(scale), e - s, V, IGNORE_INDEX,
                                                         0, _ext.ptr(rows) if det else 0, 0.0,
@@ -137,6 +147,9 @@ class LMHeadCEFn(torch.autograd.Function):
             else:
                 dl8 = None
                 logits = torch.mm(yc.float(), w.float().t())
+                if softcap:
+                    th = torch.tanh(logits / softcap)
+                    logits = softcap * th
                 lse = torch.logsumexp(logits, dim=-1)
                 ok = tc != IGNORE_INDEX
                 tgt = torch.where(ok, tc, torch.zeros_like(tc))
@@ -148,6 +161,8 @@ class LMHeadCEFn(torch.autograd.Function):
                     p *= (1.0 + 2.0 * z_loss * lse)[:, None]
                 p.scatter_add_(1, tgt[:, None], -torch.ones_like(p[:, :1]))
                 p *= ok[:, None].to(p.dtype) * scale
+                if softcap:
+                    p *= 1.0 - th * th
                 dl = p.to(y.dtype)
             if q is not None:
                 # e5m2 dlogits (one cast; delayed scaling of slot kdy), then both gradient GEMMs in fp8
@@ -179,7 +194,7 @@ class LMHeadCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, *_):
         (dy,) = ctx.saved_tensors
-        return (dy * g.to(dy.dtype),) + (None,) * 10
+        return (dy * g.to(dy.dtype),) + (None,) * 11
 
 
 def _ce_z_launch(logits, tc, loss_sum, z_sum, scale, rows, z_coef, t8):
@@ -205,6 +220,28 @@ def _ce_z_launch(logits, tc, loss_sum, z_sum, scale, rows, z_coef, t8):
     return dl8
 
 
+def _ce_cap_launch(logits, tc, loss_sum, z_sum, scale, rows, z_coef, cap, t8):
+    """The capped CE kernel on one chunk of logits, with z-loss (``z_sum`` given) or without; otherwise as
+    ``_ce_z_launch``."""
+    n, V = logits.shape
+    rows_z = torch.empty_like(rows) if rows is not None and z_sum is not None else None
+    head = (_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc), _ext.ptr(loss_sum), _ext.ptr(z_sum), _ext.ptr(scale),
+            n, V, IGNORE_INDEX, 0, _ext.ptr(rows), _ext.ptr(rows_z), z_coef if z_sum is not None else 0.0, cap)
+    dl8 = None
+    if t8 is not None:
+        q8 = t8.alloc((n, V), logits.device)
+        rc = _ext.lib().nd_ce_cap_fwd_bwd_q8(*head, *t8.args(q8), _ext.stream_ptr(logits.device))
+        if rc == 0:
+            dl8 = q8
+        elif rc != _HIP_INVALID_VALUE:  # invalid value = shape not taken: cast separately, as the cap-free path
+            _ext.check(rc, "nd_ce_cap_fwd_bwd_q8")
+    if dl8 is None:
+        _ext.check(_ext.lib().nd_ce_cap_fwd_bwd(*head, _ext.stream_ptr(logits.device)), "nd_ce_cap_fwd_bwd")
+    if rows_z is not None:
+        z_sum += rows_z.sum()
+    return dl8
+
+
 LM_KEY = "x.lm"  # the lm head's slot pair / weight cache in Fp8Linears (ops/fp8.py fp8_projection("lm"))
 
 
@@ -215,20 +252,53 @@ def _z_coef(z_loss) -> float:
     return z
 
 
+def _cap(softcap) -> float:
+    if softcap is None:
+        return 0.0
+    if isinstance(softcap, (bool, str)):
+        raise ValueError(f"softcap must be a finite number > 0 (0 = off), got {softcap!r}")
+    c = float(softcap)
+    if not 0.0 <= c < float("inf"):  # refuses NaN too
+        raise ValueError(f"softcap must be a finite number > 0 (0 = off), got {softcap!r}")
+    return c
+
+
+def logit_softcap(logits: torch.Tensor, softcap: float) -> torch.Tensor:
+    """``softcap * tanh(logits / softcap)`` IN PLACE on a contiguous bf16 / fp32 tensor (``nd_logit_softcap`` on the
+    HIP path), returned; ``softcap`` 0 = off: nothing runs.  bf16 results are the fp32 value rounded once."""
+    c = _cap(softcap)
+    if c == 0.0 or logits.numel() == 0:
+        return logits
+    if not logits.is_contiguous():
+        raise ValueError("logit_softcap works in place on a contiguous tensor")
+    if _ext.use_hip(logits):
+        _ext.check(_ext.lib().nd_logit_softcap(_ext.ptr(logits), _ext.dtcode(logits), logits.numel(), c,
+                                               _ext.stream_ptr(logits.device)), "nd_logit_softcap")
+    else:
+        from .reference import softcap as _ref
+        logits.copy_(_ref(logits, c))
+    return logits
+
+
 def lm_head_ce(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torch.Tensor, loss_scale: float = 1.0,
                chunk_rows: int = 0, wt: torch.Tensor = None, f8=None, version: int = 0, y8=None,
-               z_loss: float = 0.0) -> torch.Tensor:
+               z_loss: float = 0.0, softcap: float = 0.0) -> torch.Tensor:
     """``wt``: optional W^T copy [d, V] for the input-gradient GEMM (see ops/linear.py).  ``f8``: the model's
     ``Fp8Linears`` for the fp8 lm head, with the weight ``version`` and ``y8``, the fused e4m3 copy of y if any.
-    ``z_loss``: the z-loss coefficient (0.0 = off); the returned loss is the objective, cross-entropy + z term."""
-    return lm_head_ce_parts(y, w, gw, targets, loss_scale, chunk_rows, wt, f8, version, y8, z_loss).loss
+    ``z_loss``: the z-loss coefficient (0.0 = off); the returned loss is the objective, cross-entropy + z term.
+    ``softcap``: the logits' soft cap C (0.0 = off): loss and gradients are those of ``C * tanh(logits / C)``."""
+    return lm_head_ce_parts(y, w, gw, targets, loss_scale, chunk_rows, wt, f8, version, y8, z_loss, softcap).loss
 
 
 def lm_head_ce_parts(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets: torch.Tensor,
                      loss_scale: float = 1.0, chunk_rows: int = 0, wt: torch.Tensor = None, f8=None, version: int = 0,
-                     y8=None, z_loss: float = 0.0) -> LMHeadLoss:
+                     y8=None, z_loss: float = 0.0, softcap: float = 0.0) -> LMHeadLoss:
     """``lm_head_ce`` with the objective's two parts beside it (``LMHeadLoss``)."""
     z = _z_coef(z_loss)
+    c = _cap(softcap)
+    if c != 0.0:
+        out = LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8, int(version), y8, z, c)
+        return LMHeadLoss(*out) if z != 0.0 else LMHeadLoss(out, out.detach(), None)
     if z == 0.0:  # today's call, argument for argument
         loss = LMHeadCEFn.apply(y, w, gw, targets, float(loss_scale), int(chunk_rows), wt, f8, int(version), y8)
         return LMHeadLoss(loss, loss.detach(), None)
@@ -237,7 +307,7 @@ def lm_head_ce_parts(y: torch.Tensor, w: torch.Tensor, gw: torch.Tensor, targets
 
 
 @torch.no_grad()
-def lm_head_loss(y: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, chunk_rows: int = 0):
+def lm_head_loss(y: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, chunk_rows: int = 0, softcap: float = 0.0):
     """Loss-only lm head for evaluation: ``(row_loss [n] fp32, row_hit [n] bool)``.
 
     Per chunk ``logits = y_c @ W^T`` (the plain projection GEMM) and ``nd_ce_loss``: one of ``lm_head_ce``'s three
@@ -245,7 +315,9 @@ def lm_head_loss(y: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, chunk_
     target is ``IGNORE_INDEX``); ``row_hit`` = the target's logit equals the row maximum (top-1, ties count, exact on
     the stored logits; False on ignored rows and on rows that hold a NaN).  Per-row stores only -- no atomics -- so
     the result is bitwise repeatable with or without the deterministic mode.  Always bf16 / fp32, never the fp8
-    lm head.  CPU / ``--ops torch``: fp32 logits, as ``lm_head_ce``."""
+    lm head.  CPU / ``--ops torch``: fp32 logits, as ``lm_head_ce``.  ``softcap`` (C > 0; 0.0 = off, today's launch):
+    ``row_loss`` on ``C * tanh(logits / C)`` (``nd_ce_loss_cap``); ``row_hit`` stays the top-1 of the stored logits."""
+    cap = _cap(softcap)
     n, V = y.shape[0], w.shape[0]
     targets = targets.reshape(-1)
     row_loss = torch.empty(n, dtype=torch.float32, device=y.device)
@@ -255,15 +327,23 @@ def lm_head_loss(y: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, chunk_
         yc, tc = y[s:e], targets[s:e]
         if hip:
             logits = mm_nt(yc, w)
+            if cap:
+                _ext.check(_ext.lib().nd_ce_loss_cap(_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc), e - s, V,
+                                                     IGNORE_INDEX, _ext.ptr(row_loss[s:e]), 0, _ext.ptr(row_hit[s:e]),
+                                                     cap, _ext.stream_ptr(y.device)), "nd_ce_loss_cap")
+                continue
             _ext.check(_ext.lib().nd_ce_loss(_ext.ptr(logits), _ext.dtcode(logits), _ext.ptr(tc), e - s, V,
                                              IGNORE_INDEX, _ext.ptr(row_loss[s:e]), 0, _ext.ptr(row_hit[s:e]),
                                              _ext.stream_ptr(y.device)), "nd_ce_loss")
         else:
             logits = torch.mm(yc.float(), w.float().t())
-            lse = torch.logsumexp(logits, dim=-1)
             ok = tc != IGNORE_INDEX
             tgt = torch.where(ok, tc, torch.zeros_like(tc))
+            hit = logits.gather(1, tgt[:, None])[:, 0] == logits.max(dim=-1).values  # on the stored logits
+            if cap:
+                logits = cap * torch.tanh(logits / cap)
+            lse = torch.logsumexp(logits, dim=-1)
             picked = logits.gather(1, tgt[:, None])[:, 0]
             row_loss[s:e] = torch.where(ok, lse - picked, torch.zeros_like(lse))
-            row_hit[s:e] = ok & (picked == logits.max(dim=-1).values) & ~torch.isnan(lse)
+            row_hit[s:e] = ok & hit & ~torch.isnan(lse)
     return row_loss, row_hit

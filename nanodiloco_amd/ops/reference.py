@@ -231,6 +231,14 @@ def shift_labels(labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor
     return F.pad(labels[:, 1:], (0, 1), value=ignore_index)
 
 
+def softcap(x: torch.Tensor, cap: float) -> torch.Tensor:
+    """Final-logit soft-capping ``cap * tanh(x / cap)`` in fp32 (docs/DESIGN.md "Logit soft-capping"); ``cap`` 0 / None
+    = off: ``x`` as it is."""
+    if not cap:
+        return x
+    return float(cap) * torch.tanh(x.float() / float(cap))
+
+
 def cross_entropy_loss(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
     return F.cross_entropy(logits.float().view(-1, logits.shape[-1]), targets.view(-1),
                            ignore_index=ignore_index, reduction="mean")

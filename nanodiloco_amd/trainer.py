@@ -64,6 +64,10 @@ class TrainArgs:
     z_loss: float = 0.0            # z-loss coefficient: the objective gains z_loss * mean(logsumexp(logits)^2) inside
                                    # the lm-head CE kernels (docs/DESIGN.md "z-loss"); 0 = off.  The logged `loss`
                                    # stays the cross-entropy, the weighted term is logged as `z_loss`
+    logit_softcap: float = 0.0     # final-logit soft-capping: the model's logits are C * tanh(logits / C), inside the
+                                   # lm-head CE kernels and wherever the model hands logits out (0 = off; the same as
+                                   # "final_logit_softcapping": C in the model config).  A resumed checkpoint's
+                                   # config.json carries it.  docs/DESIGN.md "Logit soft-capping"
     qk_norm: bool = False          # QK-norm: a per-head RMSNorm of q and k before RoPE with one learnable [head_dim]
                                    # weight each per layer (Qwen3; docs/DESIGN.md "QK-norm").  Forces the model
                                    # config's `qk_norm` key on; a resumed checkpoint's config.json turns it on as well
@@ -256,6 +260,8 @@ class Trainer:
             raise ValueError("total_steps must be a multiple of inner_steps")  # REF main.py:69
         if not 0.0 <= a.z_loss < float("inf"):  # NaN fails both comparisons
             raise ValueError(f"--z-loss must be a finite coefficient >= 0 (0 = off), got {a.z_loss}")
+        if not 0.0 <= a.logit_softcap < float("inf"):
+            raise ValueError(f"--logit-softcap must be a finite cap > 0 (0 = off), got {a.logit_softcap}")
         if a.comm_rank:
             if not 1 <= a.comm_rank <= 32:
                 raise ValueError(f"--comm-rank must be in [1, 32] columns per factor (0 = off), got {a.comm_rank}")
@@ -305,6 +311,14 @@ class Trainer:
         window = a.sliding_window or (ck.sliding_window if ck is not None else None)
         if window and window != self.llama_config.sliding_window:
             self.llama_config = dataclasses.replace(self.llama_config, sliding_window=int(window))
+        ck_cap = (ck.final_logit_softcapping or 0.0) if ck is not None else 0.0
+        if ck is not None and a.logit_softcap and float(a.logit_softcap) != float(ck_cap):
+            raise ValueError(f"--logit-softcap {a.logit_softcap:g} differs from the checkpoint's final_logit_softcapping "
+                             f"({ck_cap or 'off'}): a resumed run continues the model its config.json describes "
+                             "(drop the flag)")
+        cap = a.logit_softcap or ck_cap
+        if cap and float(cap) != float(self.llama_config.final_logit_softcapping or 0.0):
+            self.llama_config = dataclasses.replace(self.llama_config, final_logit_softcapping=float(cap))
         if str(a.per_device_batch_size).lower() == "auto":
             a.per_device_batch_size = auto_micro_batch(self.llama_config, a.seq_length, a.batch_size, e.device)
         a.per_device_batch_size = int(a.per_device_batch_size)
@@ -559,6 +573,8 @@ class Trainer:
             extra["qk_norm"] = True
         if self.llama_config.sliding_window:  # likewise: no key, no window
             extra["sliding_window"] = self.llama_config.sliding_window
+        if self.llama_config.final_logit_softcapping:  # likewise: no key, no cap
+            extra["final_logit_softcapping"] = self.llama_config.final_logit_softcapping
         save_checkpoint(self.args.checkpoint_dir, self.model, self.diloco, self.env, step, data_state=ds,
                         extra=extra)
 

@@ -2,7 +2,9 @@
 
 Directory layout (written only at outer-step boundaries, when all replicas are identical):
 
-  <dir>/config.json              HF LlamaConfig JSON (+ "architectures": ["LlamaForCausalLM"])
+  <dir>/config.json              HF LlamaConfig JSON (+ "architectures": ["LlamaForCausalLM"]); a soft-capped model
+                                 also carries "final_logit_softcapping": C, which ``--resume``, ``evaluate`` and
+                                 ``generate`` apply and stock ``transformers`` Llama ignores (docs/MIGRATING.md)
   <dir>/model.safetensors        fp32 master weights, HF key names -> ``LlamaForCausalLM.from_pretrained(dir)``
   <dir>/diloco_state.safetensors outer state shared by all workers: theta_sync, outer momentum
   <dir>/rank{r}.safetensors      per-rank inner AdamW m/v + data-generator state (``--inner-optimizer muon``: the

@@ -35,7 +35,7 @@ class GraphedMicroStep:
         # After capture they are the graph's static outputs, like the returned loss: valid until the next call
         self.ce_loss = self.z_loss = None
         self._static = None  # (loss, ce_loss, z_loss) the captured graph writes
-        self.loss_scale = self.z_coef = None
+        self.loss_scale = self.z_coef = self.softcap = None
         self.eager_fallbacks = 0
 
     def _run(self, ids, labels, loss_scale):
@@ -58,7 +58,7 @@ class GraphedMicroStep:
             return self._run(ids, labels, loss_scale)
         if self.graph is None:
             self.ids, self.labels, self.loss_scale = ids.clone(), labels.clone(), loss_scale
-            self.z_coef = self.model.z_loss
+            self.z_coef, self.softcap = self.model.z_loss, self.model.softcap
             self.model.refresh_transposed()  # nothing stale gets captured as a copy
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):  # records only; the replay below does the work
@@ -68,6 +68,8 @@ class GraphedMicroStep:
             raise ValueError("loss_scale changed after capture")
         if self.model.z_loss != self.z_coef:  # a kernel argument of the captured launches
             raise ValueError("model.z_loss changed after capture")
+        if self.model.softcap != self.softcap:  # likewise
+            raise ValueError("model.softcap changed after capture")
         self.model.refresh_transposed()  # W^T copies the captured dgrad GEMMs read
         self.ids.copy_(ids, non_blocking=True)
         self.labels.copy_(labels, non_blocking=True)
