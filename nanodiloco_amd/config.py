@@ -103,6 +103,9 @@ class LlamaConfig:
     # final-logit soft-capping (Gemma 2's key): the model's logits are C * tanh(logits / C); None / 0 = off
     # (docs/DESIGN.md "Logit soft-capping")
     final_logit_softcapping: Optional[float] = None
+    # attention logit soft-capping (Gemma 2's key): the attention scores are C * tanh(scale q.k / C) before the mask
+    # and the softmax, in every layer; None / 0 = off (docs/DESIGN.md "Attention soft-capping")
+    attn_logit_softcapping: Optional[float] = None
     architectures: Optional[list] = None
     extra: Dict[str, Any] = dataclasses.field(default_factory=dict)
 
@@ -116,6 +119,9 @@ class LlamaConfig:
         cap = self.final_logit_softcapping
         if cap is not None and not isinstance(cap, (bool, str)) and cap == 0:
             self.final_logit_softcapping = None
+        cap = self.attn_logit_softcapping
+        if cap is not None and not isinstance(cap, (bool, str)) and cap == 0:
+            self.attn_logit_softcapping = None
         # transformers>=5 stores rope_theta inside rope_parameters; accept both spellings.
         rp = self.extra.get("rope_parameters")
         if isinstance(rp, dict) and "rope_theta" in rp:
@@ -161,6 +167,8 @@ class LlamaConfig:
             del d["sliding_window"]  # likewise
         if not self.final_logit_softcapping:
             del d["final_logit_softcapping"]  # likewise
+        if not self.attn_logit_softcapping:
+            del d["attn_logit_softcapping"]  # likewise
         if d.get("architectures") is None:
             d["architectures"] = ["LlamaForCausalLM"]
         return d
@@ -192,6 +200,10 @@ class LlamaConfig:
         if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, float))
                                 or not 0.0 < float(cap) < float("inf")):  # NaN fails both comparisons
             raise ValueError(f"final_logit_softcapping must be a finite number > 0 (0 / null = off), got {cap!r}")
+        cap = self.attn_logit_softcapping
+        if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, float))
+                                or not 0.0 < float(cap) < float("inf")):
+            raise ValueError(f"attn_logit_softcapping must be a finite number > 0 (0 / null = off), got {cap!r}")
         if self.rope_scaling not in (None, {}) and self.rope_scaling.get("rope_type", self.rope_scaling.get("type")) not in (
             "default", "linear", "llama3"):
             raise ValueError(f"unsupported rope_scaling {self.rope_scaling}")

@@ -26,6 +26,7 @@
 // Causal: tiles past the diagonal are never loaded; fully masked (wave, tile) pairs are skipped;
 // the longest query / key blocks are dispatched first.
 #include "lds_dma.h"
+#include "softcap.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -395,6 +396,12 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // tiles wholly before a wave's first window are not multiplied, dK/dV's query walk ends with the block's last key's
 // window.
 constexpr int MASK_NONE = 0, MASK_PAD = 1, MASK_DOC = 2, MASK_WIN = 3;
+// Attention soft-capping (docs/DESIGN.md "Attention soft-capping"): a kernel instantiated with one trailing CapArgs
+// (CA = {CapArgs}; the launchers are in attn_softcap.hip) turns every raw score s = q.k into z = C tanh(s scale / C)
+// before the mask and the softmax; with the empty pack every `if constexpr (CAP)` is gone and the kernel is the
+// uncapped one, instruction for instruction.  The capped kernels keep t = tanh(u) in the score registers and fold C
+// into the exponent's multiplier: c = C log2(e) where the uncapped kernels have scale log2(e), so masks, running
+// max, LSE (log2 domain, of the capped scores) and exponent run through the same code.
 // MASK_DOC keeps no per-lane bound live across the tile loop (the head_dim-64 forward and dK/dV kernels sit exactly
 // on their register budgets): a wave's 32 rows are consecutive tokens, so their bounds are the bound of the
 // document that is open at the wave's edge (one scalar) plus one bit per row -- "a document starts / ends here" --
@@ -419,16 +426,19 @@ __device__ __forceinline__ uint32_t bit_range(int lo, int hi) {
   const int l = min(max(lo, 0), 32), u = min(max(hi, 0), 32);
   return (uint32_t)((1ull << u) - 1) & (uint32_t)(~0ull << l);
 }
-template <int HD, bool ROPE, bool DMA = false, int MASK = MASK_NONE, int ABL = 0, int NW = 4>  // DMA: LDS-DMA K/V staging (!ROPE, T % 64 == 0)
-__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 4 : 3)) attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+template <int HD, bool ROPE, bool DMA = false, int MASK = MASK_NONE, int ABL = 0, int NW = 4, class... CA>  // DMA: LDS-DMA K/V staging (!ROPE, T % 64 == 0)
+__global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA && !has_cap<CA...>) ? 4 : 3)) attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
                                                           float* __restrict__ LSE, int B, int nh, int nkv, int T,
                                                           int64_t ld, int64_t ldo, float scale,
                                                           const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                           const int* __restrict__ KS, float thr, int order,
-                                                          int window = 0) {
+                                                          int window = 0, CA... ca) {
   constexpr int BN = 64, NT = HD / 16, NO = HD / 32;
   constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC, WIN = MASK == MASK_WIN;
+  constexpr bool CAP = has_cap<CA...>;
+  static_assert(sizeof...(CA) == (CAP ? 1 : 0), "at most one trailing argument, a CapArgs");
+  static_assert(!CAP || (!ROPE && ABL == 0 && NW == 4), "soft-capping: default block shape, plain softmax variant");
   static_assert(!DOC || (DMA && ABL == 0 && NW == 4), "document mask: default LDS-DMA kernel, plain softmax variant");
   static_assert(!WIN || (!ROPE && ABL == 0 && NW == 4), "sliding window: default block shape, plain softmax variant");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * BN * HD];
@@ -471,7 +481,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
     dw.edge = dsw0;
     dw.bits = (uint32_t)__builtin_amdgcn_ballot_w64(ds == qi);  // lanes l and l + 32 hold the same row
   }
-  const float c = scale * LOG2E;
+  // CAP: ucap = scale / C turns a raw score into tanh's argument, c = C log2(e) a tanh into the log2-domain score
+  const float ucap = scale * cap_of(ca...).inv;
+  const float c = CAP ? cap_of(ca...).cap * LOG2E : scale * LOG2E;
   const bf16_t* Qb = Q + (int64_t)b * T * ld + (int64_t)head * HD;
   const bf16_t* Kb = K + (int64_t)b * T * ld + (int64_t)kvh * HD;
   const bf16_t* Vb = V + (int64_t)b * T * ld + (int64_t)kvh * HD;
@@ -558,6 +570,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : (HD == 64 && DMA) ? 
           if constexpr (ABL & 16) s[kt][t] += (float)ka[kt][t][0];
           else s[kt] = mfma32(ka[kt][t], qf[t], s[kt]);
         }
+      }
+      if constexpr (CAP) {  // every score, masked or not: the mask below overwrites, |t| <= 1 keeps the max finite
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[kt][r] = cap_tanh(s[kt][r] * ucap);
       }
       ND_STAMP(stp.mark(3);)
       if constexpr (ABL & 4) {
@@ -756,7 +774,10 @@ __global__ void __launch_bounds__(256) attn_bwd_pre_kernel(const bf16_t* __restr
 // half of O, dots, and one lane^32 exchange gives delta = rowsum(dO * O); the kernel then writes
 // -delta and -LSE/c (the seeds of the dK/dV kernel, which therefore runs after this one).
 // NW: waves per workgroup (8 = 256-query blocks, LDS-DMA only; see attn_fwd_kernel)
-template <int HD, bool ROPE, bool ROPE_OUT, bool DMA = false, bool PRE = false, int MASK = MASK_NONE, int NW = 4>  // DMA: LDS-DMA K/V staging; MASK: see attn_fwd_kernel
+// CAP (one trailing CapArgs; fused LDS-DMA form only): t = tanh(s scale / C) and d = 1 - t^2 from one cap_tanh per
+// score, p = exp2(C log2e t - lse) through the uncapped code (c = C log2e), dS = p (dP - delta) d; NL gets -lse in the
+// log2 domain, NOT divided by c: the capped dK/dV kernel cannot seed its score accumulator with it (see there).
+template <int HD, bool ROPE, bool ROPE_OUT, bool DMA = false, bool PRE = false, int MASK = MASK_NONE, int NW = 4, class... CA>  // DMA: LDS-DMA K/V staging; MASK: see attn_fwd_kernel
 __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                              const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
                                                              const float* __restrict__ LSE, const float* __restrict__ DELTA,
@@ -767,9 +788,12 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
                                                              float* __restrict__ NL = nullptr,
                                                              float* __restrict__ ND = nullptr,
                                                              const int* __restrict__ KS = nullptr, int order = 0,
-                                                             int window = 0) {
+                                                             int window = 0, CA... ca) {
   constexpr int BN = 64, NT = HD / 16, NO = HD / 32;
   constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC, WIN = MASK == MASK_WIN;
+  constexpr bool CAP = has_cap<CA...>;
+  static_assert(sizeof...(CA) == (CAP ? 1 : 0), "at most one trailing argument, a CapArgs");
+  static_assert(!CAP || (DMA && PRE && NW == 4), "soft-capping: fused LDS-DMA backward, default block shape");
   static_assert(!DOC || (DMA && PRE), "document mask: fused LDS-DMA backward only");
   static_assert(!WIN || (DMA && PRE && NW == 4), "sliding window: fused LDS-DMA backward, default block shape");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * BN * HD];
@@ -804,7 +828,8 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
     dw.edge = dsw0;
     dw.bits = (uint32_t)__builtin_amdgcn_ballot_w64(ds == qi);
   }
-  const float c = scale * LOG2E;
+  const float ucap = scale * cap_of(ca...).inv;  // see attn_fwd_kernel
+  const float c = CAP ? cap_of(ca...).cap * LOG2E : scale * LOG2E;
   const bf16_t* Qb = Q + (int64_t)b * T * ld + (int64_t)head * HD;
   const bf16_t* dOb = dO + (int64_t)b * T * ldo + (int64_t)head * HD;
   const bf16_t* Kb = K + (int64_t)b * T * ld + (int64_t)kvh * HD;
@@ -835,7 +860,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
     dlt = pair_sum32(acc);
     if (qi < T && h == 0) {
       ND[rowstat + qi] = -dlt;
-      NL[rowstat + qi] = -lse * (1.f / c);
+      NL[rowstat + qi] = CAP ? -lse : -lse * (1.f / c);
     }
   } else {
     dlt = qi < T ? DELTA[rowstat + qi] : 0.f;
@@ -916,6 +941,15 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
           dp = mfma32(va[t], dof[t], dp);
         }
         ND_STAMP(stp.mark(4);)
+        [[maybe_unused]] f32x16 dcap;  // CAP: 1 - t^2 of every score, while s holds t
+        if constexpr (CAP) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float d;
+            s[r] = cap_tanh(s[r] * ucap, d);
+            dcap[r] = d;
+          }
+        }
         if (!diag) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) dp[r] = fexp2(fmaf(s[r], c, -lse)) * (dp[r] - dlt);
@@ -936,6 +970,10 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dq_kern
             const float p = (key <= qi && key < T && qi < T && (!(PAD || WIN) || key >= lo)) ? fexp2(fmaf(s[r], c, -lse)) : 0.f;
             dp[r] = p * (dp[r] - dlt);
           }
+        }
+        if constexpr (CAP) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dp[r] *= dcap[r];
         }
         ND_STAMP(stp.mark(5);)
 #pragma unroll
@@ -1127,6 +1165,9 @@ __global__ void __launch_bounds__(256, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_kernel
 }
 
 // ------------------------------------------------------------------------------------ launchers
+// attn_softcap.hip includes this file for the kernel templates alone (ND_ATTN_KERNELS_ONLY) and has the launchers of
+// their capped instantiations; everything that may exist once per library is inside the #ifndef blocks.
+#ifndef ND_ATTN_KERNELS_ONLY
 // Launch-time switches, parsed when the library loads (never per launch; nd_env_reload() in env.hip runs the
 // same parse again, for tests that flip a switch inside one process).  Only correct variants are
 // selectable in the product library; the wrong-result timing ablations (ABL bits other than the
@@ -1187,6 +1228,11 @@ static int attn_order() { return g_attn.order; }
 // bit 0: a (batch, head)'s key blocks consecutive on one XCD (MHA only); bit 1: descending query walk
 // (LDS-DMA dK/dV kernel)
 static int dkdv_order(int nh, int nkv) { return ((g_attn.dkdv_order & 1) && nh == nkv ? 1 : 0) | (g_attn.dkdv_order & 2); }
+namespace nd {  // the three switches the capped launchers (attn_softcap.hip) share with these
+float attn_env_thr() { return g_attn.thr; }
+int attn_env_order() { return attn_order(); }
+int attn_env_dkdv_order(int nh, int nkv) { return dkdv_order(nh, nkv); }
+}  // namespace nd
 
 // wrong-result ablation builds only (timing): ABL bits of attn_fwd_kernel / attn_bwd_dkdv_dma_kernel
 #ifdef ND_ABLATION
@@ -1363,6 +1409,7 @@ __global__ void __launch_bounds__(256) attn_neg_stats_kernel(const float* __rest
     nd[i] = -delta[i];
   }
 }
+#endif  // ND_ATTN_KERNELS_ONLY
 
 // NW: waves per workgroup (8 = 256-key blocks: every Q / dO tile DMA'd once per 256 keys)
 // ABL (timing ablations, wrong results; ND_ATTN_DKDV_ABL): 1 no Q / dO / statistics DMA and no vmcnt wait,
@@ -1370,13 +1417,19 @@ __global__ void __launch_bounds__(256) attn_neg_stats_kernel(const float* __rest
 // read only in the first step
 // NB: Q / dO / statistics buffers in LDS; tile it + NB - 1 is in flight while tile it is computed
 // MASK_DOC: KS = doc_end [B, T]; the query-tile walk ends with the document of the block's last key
-template <int HD, bool ROPE_OUT, int BQ = 64, int MASK = MASK_NONE, int NW = 4, int ABL = 0, int NB = 2>
+// CAP (one trailing CapArgs): P = exp2(C log2e tanh(s scale / C) - lse) is no function of s - lse / c, so the score
+// accumulator cannot be seeded with the row statistic: the S MFMAs start from zero and NL holds -lse itself (log2
+// domain; the capped dQ kernel writes it so).  Each score then takes one cap_tanh (t and d = 1 - t^2), one fma with
+// its row's -lse, read from lse_s at use (four 16-B LDS reads per step; held across the MFMAs they would be 16 more
+// live VGPRs on a kernel that sits on its budget at head_dim 64), and the uncapped exponent with c = 1.  dp is still
+// seeded with -delta, so it is dP - delta when the MFMAs end and takes d at once: dS = P ((dP - delta) d).
+template <int HD, bool ROPE_OUT, int BQ = 64, int MASK = MASK_NONE, int NW = 4, int ABL = 0, int NB = 2, class... CA>
 __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dma_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ NL, const float* __restrict__ ND, bf16_t* __restrict__ dK,
     bf16_t* __restrict__ dV, int B, int nh, int nkv, int T, int64_t ld, int64_t ldo, float scale,
     const float* __restrict__ cosT, const float* __restrict__ sinT, const int* __restrict__ KS, int order,
-    int window = 0) {
+    int window = 0, CA... ca) {
   constexpr int NT = HD / 16, NO = HD / 32;
   constexpr int CPR = HD / 8;              // 16-B chunks per row
   constexpr int RPI = 64 / CPR;            // rows per 1-KiB DMA wave-instruction
@@ -1384,6 +1437,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
   constexpr int KB = 32 * NW;              // keys per workgroup
   constexpr bool PAD = MASK == MASK_PAD, DOC = MASK == MASK_DOC, WIN = MASK == MASK_WIN;
   static_assert(!WIN || (NW == 4 && ABL == 0 && NB == 2), "sliding window: default block shape");
+  constexpr bool CAP = has_cap<CA...>;
+  static_assert(sizeof...(CA) == (CAP ? 1 : 0), "at most one trailing argument, a CapArgs");
+  static_assert(!CAP || (NW == 4 && ABL == 0 && NB == 2), "soft-capping: default block shape");
   __shared__ __attribute__((aligned(16))) bf16_t Qs[NB * BQ * HD];
   __shared__ __attribute__((aligned(16))) bf16_t dOs[NB * BQ * HD];
   __shared__ __attribute__((aligned(16))) float lse_s[NB * BQ];
@@ -1415,7 +1471,9 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
     dw.edge = dew1;
     dw.bits = (uint32_t)__builtin_amdgcn_ballot_w64(de == key + 1);  // lanes l and l + 32 hold the same key
   }
-  const float c = scale * LOG2E;
+  // CAP: ucap = scale / C, ccap = C log2(e); the -lse term is added before the exponent, whose own multiplier is 1
+  const float ucap = scale * cap_of(ca...).inv, ccap = cap_of(ca...).cap * LOG2E;
+  const float c = CAP ? 1.f : scale * LOG2E;
   const bf16_t* Kb = K + (int64_t)b * T * ld + (int64_t)kvh * HD;
   const bf16_t* Vb = V + (int64_t)b * T * ld + (int64_t)kvh * HD;
 
@@ -1546,7 +1604,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
         const int qr = qs * 32 + 8 * r4 + 4 * h;
-        const float4 l4 = *reinterpret_cast<const float4*>(lt + qr);
+        const float4 l4 = CAP ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(lt + qr);
         const float4 d4 = *reinterpret_cast<const float4*>(dt + qr);
         s[4 * r4 + 0] = l4.x; s[4 * r4 + 1] = l4.y; s[4 * r4 + 2] = l4.z; s[4 * r4 + 3] = l4.w;
         dp[4 * r4 + 0] = d4.x; dp[4 * r4 + 1] = d4.y; dp[4 * r4 + 2] = d4.z; dp[4 * r4 + 3] = d4.w;
@@ -1574,6 +1632,20 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
       ND_STAMP(stp.mark(3);)
       const bool diag = (kw0 + 31 > qsub) || (qsub + 31 >= T) || (key >= T) || (PAD && kw0 < ks) || (DOC && qsub + 31 >= dew0) ||
                         (WIN && (qsub + 31 >= kw0 + window || kw0 < ks));  // WIN: reaches the FIRST key's window end
+      if constexpr (CAP) {
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const float4 l4 = *reinterpret_cast<const float4*>(lt + qs * 32 + 8 * r4 + 4 * h);  // -lse of the rows
+          const float nl[4] = {l4.x, l4.y, l4.z, l4.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int r = 4 * r4 + q;
+            float d;
+            s[r] = fmaf(cap_tanh(s[r] * ucap, d), ccap, nl[q]);
+            dp[r] *= d;  // dp is dP - delta already (the seed): d needs no register of its own
+          }
+        }
+      }
       if constexpr ((ABL & 4) != 0) {
       } else if (!diag) {
 #pragma unroll
@@ -1629,6 +1701,7 @@ __global__ void __launch_bounds__(64 * NW, (HD >= 128 ? 1 : 2)) attn_bwd_dkdv_dm
   ND_STAMP(stp.mark(6); stp.flush(1);)
 }
 
+#ifndef ND_ATTN_KERNELS_ONLY
 template <int HD, bool ROPE, bool ROPE_OUT, bool PAD>
 static void bwd_launch_t(const void* q, const void* k, const void* v, const void* dout, const float* lse,
                          const float* delta, void* dq, void* dk, void* dv, float* ws, int B, int nh, int nkv, int T,
@@ -1883,3 +1956,4 @@ ND_API int nd_attn_bwd_fused_win(const void* q, const void* k, const void* v, co
     default: return (int)hipErrorInvalidValue;
   }
 }
+#endif  // ND_ATTN_KERNELS_ONLY

@@ -27,6 +27,7 @@
 // fma so that the bits do not depend on what the compiler contracts; key pos[b] is taken from these registers, never
 // read back from the cache.  Slots beyond pos[b] are never loaded.
 #include "common.h"
+#include "softcap.h"
 
 using namespace nd;
 
@@ -61,12 +62,16 @@ __device__ __forceinline__ void unpack8(uint4 a, float* v) {
 
 // HD: head dimension; REP: compile-time bound (power of two) of the run-time group size rep = nh / nkv <= REP.
 // Query slots r >= rep repeat the group's last head and are not written.
-template <int HD, int REP>
+// CA: empty, or one CapArgs (attention soft-capping; the launchers are in attn_decode_cap.hip): the scores become
+// C log2(e) tanh(q.k scale / C), and `scale2` is then the plain scale -- the log2(e) goes into the cap's factor.
+template <int HD, int REP, class... CA>
 __global__ void __launch_bounds__(64 * DEC_WAVES)
 attn_decode_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ cosT, const float* __restrict__ sinT,
                    const int* __restrict__ pos, const int* __restrict__ kstart, bf16_t* __restrict__ kcache,
                    bf16_t* __restrict__ vcache, float* __restrict__ part_o, float* __restrict__ part_ml, int nh,
-                   int nkv, int rep, int S_max, int64_t ld, float scale2, int window) {
+                   int nkv, int rep, int S_max, int64_t ld, float scale2, int window, CA... ca) {
+  constexpr bool CAP = has_cap<CA...>;
+  static_assert(sizeof...(CA) == (CAP ? 1 : 0), "at most one trailing argument, a CapArgs");
   constexpr int LPR = HD / 8;       // lanes per K/V row
   constexpr int KPI = 64 / LPR;     // rows per wave-wide load
   constexpr int ITER = KPW / KPI;   // loads per lane for the wave's keys
@@ -163,7 +168,9 @@ attn_decode_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ cos
       for (int j = 0; j < 8; ++j) acc = __builtin_fmaf(q[r][j], kf[j], acc);
 #pragma unroll
       for (int o = LPR / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      s[r][it] = valid ? acc * scale2 : -INFINITY;
+      if constexpr (CAP) acc = cap_tanh(acc * (scale2 * cap_of(ca...).inv)) * (cap_of(ca...).cap * LOG2E);
+      else acc *= scale2;
+      s[r][it] = valid ? acc : -INFINITY;
     }
   }
 
@@ -277,14 +284,14 @@ __global__ void attn_decode_combine_kernel(const float* __restrict__ part_o, con
   o[((int64_t)b * nh + h) * hd + d] = f2bf(L > 0.f ? O / L : 0.f);  // no key at all: 0, as the training kernels
 }
 
-template <int HD>
+template <int HD, class... CA>
 int launch(const bf16_t* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart, bf16_t* kc,
            bf16_t* vc, float* part_o, float* part_ml, int B, int nh, int nkv, int rep, int S_max, int64_t ld,
-           float scale2, int window, hipStream_t st) {
+           float scale2, int window, hipStream_t st, CA... ca) {
   const dim3 grid((unsigned)nkv, (unsigned)B, (unsigned)((S_max + SPLIT - 1) / SPLIT)), block(64 * DEC_WAVES);
 #define ND_DECODE(R)                                                                                            \
-  hipLaunchKernelGGL((attn_decode_kernel<HD, R>), grid, block, 0, st, qkv, cosT, sinT, pos, kstart, kc, vc, part_o, \
-                     part_ml, nh, nkv, rep, S_max, ld, scale2, window)
+  hipLaunchKernelGGL((attn_decode_kernel<HD, R, CA...>), grid, block, 0, st, qkv, cosT, sinT, pos, kstart, kc, vc, part_o, \
+                     part_ml, nh, nkv, rep, S_max, ld, scale2, window, ca...)
   if (rep == 1) ND_DECODE(1);
   else if (rep == 2) ND_DECODE(2);
   else if (rep <= 4) ND_DECODE(4);
@@ -295,16 +302,20 @@ int launch(const bf16_t* qkv, const float* cosT, const float* sinT, const int* p
 
 }  // namespace
 
+#ifndef ND_DECODE_KERNELS_ONLY  // attn_decode_cap.hip includes this file for everything but the library entries
 // The compile-time chunk length of the key partition (tests aim at its edges).
 ND_API int nd_attn_decode_split() { return SPLIT; }
+#endif
 
 // Workspace: part_o [B, nkv, nchunks, rep, hd] fp32, part_ml [B, nkv, nchunks, rep, 2] fp32, nchunks = ceil(S_max / SPLIT).
 // `ld`: row stride of qkv in elements.  The tables must hold at least S_max rows; 0 <= pos[b] < S_max (a position
 // outside writes nothing and gives o = 0).
 // window: 0 = none; W >= 1 = sliding window, keys max(kstart[b], pos[b] - W + 1) .. pos[b] (nd_attn_decode_win).
+// ca: empty, or one CapArgs (nd_attn_decode_cap, attn_decode_cap.hip): the capped kernel; the combine is the same.
+template <class... CA>
 static int decode_impl(const void* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart,
                        void* kcache, void* vcache, float* part_o, float* part_ml, void* o, int B, int nh, int nkv,
-                       int hd, int S_max, int64_t ld, float scale, int window, hipStream_t st) {
+                       int hd, int S_max, int64_t ld, float scale, int window, hipStream_t st, CA... ca) {
   if (B < 1 || B > 65535 || nh < 1 || nkv < 1 || nkv > 65535 || nh % nkv || nh / nkv > 8 || S_max < 1 ||
       (S_max + SPLIT - 1) / SPLIT > 65535)
     return (int)hipErrorInvalidValue;
@@ -317,14 +328,14 @@ static int decode_impl(const void* qkv, const float* cosT, const float* sinT, co
     return (int)hipErrorInvalidValue;
   if (((uintptr_t)o & 1) || ((uintptr_t)pos & 3) || ((uintptr_t)kstart & 3)) return (int)hipErrorInvalidValue;
   const int rep = nh / nkv;
-  const float scale2 = scale * LOG2E;
+  const float scale2 = sizeof...(CA) ? scale : scale * LOG2E;  // capped: see attn_decode_kernel
   const bf16_t* x = reinterpret_cast<const bf16_t*>(qkv);
   bf16_t* kc = reinterpret_cast<bf16_t*>(kcache);
   bf16_t* vc = reinterpret_cast<bf16_t*>(vcache);
   int err;
-  if (hd == 32) err = launch<32>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st);
-  else if (hd == 64) err = launch<64>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st);
-  else err = launch<128>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st);
+  if (hd == 32) err = launch<32>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st, ca...);
+  else if (hd == 64) err = launch<64>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st, ca...);
+  else err = launch<128>(x, cosT, sinT, pos, kstart, kc, vc, part_o, part_ml, B, nh, nkv, rep, S_max, ld, scale2, window, st, ca...);
   if (err) return err;
   const int nchunks = (S_max + SPLIT - 1) / SPLIT;
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)nh, (unsigned)B), dim3((unsigned)hd), 0, st, part_o,
@@ -332,6 +343,7 @@ static int decode_impl(const void* qkv, const float* cosT, const float* sinT, co
   ND_LAUNCH_CHECK();
 }
 
+#ifndef ND_DECODE_KERNELS_ONLY
 ND_API int nd_attn_decode(const void* qkv, const float* cosT, const float* sinT, const int* pos, const int* kstart,
                           void* kcache, void* vcache, float* part_o, float* part_ml, void* o, int B, int nh, int nkv,
                           int hd, int S_max, int64_t ld, float scale, hipStream_t st) {
@@ -350,3 +362,4 @@ ND_API int nd_attn_decode_win(const void* qkv, const float* cosT, const float* s
   return decode_impl(qkv, cosT, sinT, pos, kstart, kcache, vcache, part_o, part_ml, o, B, nh, nkv, hd, S_max, ld, scale,
                      window, st);
 }
+#endif  // ND_DECODE_KERNELS_ONLY

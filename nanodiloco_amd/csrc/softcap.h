@@ -3,6 +3,7 @@
 // and the one formulation of tanh and its derivative that all of them share.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 namespace nd {
 
@@ -14,6 +15,13 @@ struct CapArgs {
 // a cap a launcher accepts: finite and > 0 (refuses NaN too)
 inline bool cap_ok(float c) { return c > 0.f && c <= 3.0e38f; }
 inline CapArgs cap_args(float c) { return CapArgs{c, 1.f / c}; }
+
+// A kernel template that ends in a parameter pack `CA... ca` is capped when the pack is one CapArgs and the plain
+// kernel, instruction for instruction, when it is empty (the attention kernels).
+template <class... CA>
+constexpr bool has_cap = (std::is_same_v<CapArgs, CA> || ...);
+__device__ __forceinline__ CapArgs cap_of() { return CapArgs{0.f, 0.f}; }
+__device__ __forceinline__ CapArgs cap_of(const CapArgs& c) { return c; }
 
 // t = tanh(u) and d = 1 - t^2 from one v_exp_f32 and one v_rcp_f32: with e = exp(-2|u|) in [0, 1],
 //   t = sign(u) (1 - e) / (1 + e)        d = 4 e / (1 + e)^2

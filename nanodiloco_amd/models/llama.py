@@ -183,7 +183,8 @@ class LlamaForCausalLM:
                                             c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps,
                                             inplace=True)
         o = ops.attention(qkv, cos, sin, B, T, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
-                          inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc, window=c.sliding_window)
+                          inplace=True, kstart=kstart, rotated=rotated, doc_bounds=doc, window=c.sliding_window,
+                          softcap=c.attn_logit_softcapping)
         if cache is not None:
             # prefill: the HIP path has rotated q|k inside qkv by now (in place, or in the GEMM epilogue); the
             # PyTorch path leaves its input alone and cache_fill rotates k itself

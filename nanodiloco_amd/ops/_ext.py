@@ -157,12 +157,16 @@ def _declare(L: ctypes.CDLL):
         # sliding window (+ optional key start): ..., ks, window, stream
         "nd_attn_fwd_win": [P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, P, I, P],
         "nd_attn_bwd_fused_win": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, I, P],
+        # soft-capping under any mask: ..., scale, ks, doc_start, doc_end, window, cap, stream (csrc/attn_softcap.hip)
+        "nd_attn_fwd_cap": [P, P, P, P, P, I, I, I, I, I, L64, L64, F, P, P, P, I, F, P],
+        "nd_attn_bwd_fused_cap": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P, P, P, I, F, P],
         "nd_attn_bwd_pre": [P, P, P, I, I, I, L64, L64, P],
         "nd_attn_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
         "nd_attn_bwd_fused": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, L64, P, P, F, I, P],
         # single-query attention against a KV cache, RoPE + append fused, split-KV + combine (csrc/attn_decode.hip)
         "nd_attn_decode": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, P],
         "nd_attn_decode_win": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, I, P],
+        "nd_attn_decode_cap": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, I, F, P],  # ..., window, cap, stream
         "nd_attn_decode_split": [],
         # mlp
         "nd_swiglu_fwd": [P, P, I, L64, I, P],

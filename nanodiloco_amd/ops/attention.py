@@ -17,6 +17,8 @@ document and ``attention(..., doc_bounds=...)`` runs ``nd_attn_fwd_doc`` / ``nd_
 causal attention in the same kernels, which skip the key / query tiles that lie wholly outside a block's documents.
 Sliding window (``attention(..., window=W)``, W < T): ``nd_attn_fwd_win`` / ``nd_attn_bwd_fused_win`` -- query q sees keys
 max(kstart, q - W + 1) .. q; the LDS-DMA kernels skip the key / query tiles that lie wholly outside a block's windows.
+Soft-capping (``attention(..., softcap=C)``): ``nd_attn_fwd_cap`` / ``nd_attn_bwd_fused_cap`` -- the capped instantiations
+of the same kernels under any of these masks; scores become C tanh(scale q.k / C) before the mask and the softmax.
 GQA (nkv < nh) is handled by head-index mapping inside the kernels (no K/V repetition).
 """
 from __future__ import annotations
@@ -65,7 +67,7 @@ class FlashAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, B, T, nh, nkv, hd, kstart=None, rotated=False, doc_start=None, doc_end=None,
-                window=None):
+                window=None, softcap=None):
         ld = qkv.shape[1]
         if not rotated:  # else the projection GEMM's epilogue already rotated q|k
             _rope(qkv, cos, sin, B, T, nh, nkv, hd, inverse=False)
@@ -75,7 +77,13 @@ class FlashAttnFn(torch.autograd.Function):
         lse = torch.empty(B, nh, T, dtype=torch.float32, device=qkv.device)
         L = _ext.lib()
         ks = _ext.ptr(kstart) if kstart is not None else 0
-        if window is not None:  # a real window (< T): ops.attention never passes another
+        if softcap is not None:  # the capped kernels, under whichever mask
+            _ext.check(L.nd_attn_fwd_cap(_ext.ptr(qkv), _ext.ptr(k), _ext.ptr(v), _ext.ptr(o), _ext.ptr(lse),
+                                         B, nh, nkv, T, hd, ld, nh * hd, float(hd ** -0.5), ks,
+                                         _ext.ptr(doc_start) if doc_start is not None else 0,
+                                         _ext.ptr(doc_end) if doc_end is not None else 0, int(window or 0),
+                                         float(softcap), _ext.stream_ptr(qkv.device)), "nd_attn_fwd_cap")
+        elif window is not None:  # a real window (< T): ops.attention never passes another
             _ext.check(L.nd_attn_fwd_win(_ext.ptr(qkv), _ext.ptr(k), _ext.ptr(v), _ext.ptr(o), _ext.ptr(lse),
                                          B, nh, nkv, T, hd, ld, nh * hd, 0, 0, float(hd ** -0.5), ks, int(window),
                                          _ext.stream_ptr(qkv.device)), "nd_attn_fwd_win")
@@ -91,6 +99,7 @@ class FlashAttnFn(torch.autograd.Function):
         ctx.kstart = kstart
         ctx.doc = (doc_start, doc_end) if doc_start is not None else None
         ctx.window = window
+        ctx.softcap = softcap
         ctx.dims = (B, T, nh, nkv, hd)
         return o
 
@@ -103,6 +112,22 @@ class FlashAttnFn(torch.autograd.Function):
         L = _ext.lib()
         dev = do.device
         ks = _ext.ptr(ctx.kstart) if ctx.kstart is not None else 0
+        if ctx.softcap is not None:  # soft-capping: the fused LDS-DMA backward is the only one
+            if T % 64:
+                raise ValueError(f"soft-capped attention has no backward for T % 64 != 0 (T = {T})")
+            dqkv = torch.empty_like(qkv)
+            k, v = qkv[:, nh * hd:], qkv[:, (nh + nkv) * hd:]
+            dk, dv = dqkv[:, nh * hd:], dqkv[:, (nh + nkv) * hd:]
+            ws = torch.empty(2, B, nh, T, dtype=torch.float32, device=dev)
+            doc = ctx.doc or (None, None)
+            _ext.check(L.nd_attn_bwd_fused_cap(_ext.ptr(qkv), _ext.ptr(k), _ext.ptr(v), _ext.ptr(o), _ext.ptr(do),
+                                               _ext.ptr(lse), _ext.ptr(dqkv), _ext.ptr(dk), _ext.ptr(dv), _ext.ptr(ws),
+                                               B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
+                                               float(hd ** -0.5), 2, ks,
+                                               _ext.ptr(doc[0]) if doc[0] is not None else 0,
+                                               _ext.ptr(doc[1]) if doc[1] is not None else 0, int(ctx.window or 0),
+                                               float(ctx.softcap), _ext.stream_ptr(dev)), "nd_attn_bwd_fused_cap")
+            return (dqkv,) + (None,) * 13
         if ctx.window is not None:  # sliding window: the fused LDS-DMA backward is the only one
             if T % 64:
                 raise ValueError(f"sliding-window attention has no backward for T % 64 != 0 (T = {T})")
@@ -115,7 +140,7 @@ class FlashAttnFn(torch.autograd.Function):
                                                B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
                                                float(hd ** -0.5), 2, ks, int(ctx.window), _ext.stream_ptr(dev)),
                        "nd_attn_bwd_fused_win")
-            return (dqkv,) + (None,) * 12
+            return (dqkv,) + (None,) * 13
         if ctx.doc is not None:  # document mode: the fused LDS-DMA backward is the only one
             dqkv = torch.empty_like(qkv)
             k, v = qkv[:, nh * hd:], qkv[:, (nh + nkv) * hd:]
@@ -126,7 +151,7 @@ class FlashAttnFn(torch.autograd.Function):
                                                B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
                                                float(hd ** -0.5), 2, _ext.ptr(ctx.doc[0]), _ext.ptr(ctx.doc[1]),
                                                _ext.stream_ptr(dev)), "nd_attn_bwd_fused_doc")
-            return (dqkv,) + (None,) * 12
+            return (dqkv,) + (None,) * 13
         if _FUSED_STATS["enabled"] and T % 64 == 0:
             # dQ kernel computes delta = rowsum(dO * O) itself and seeds the dK/dV kernel
             dqkv = torch.empty_like(qkv)
@@ -137,7 +162,7 @@ class FlashAttnFn(torch.autograd.Function):
                                               _ext.ptr(lse), _ext.ptr(dqkv), _ext.ptr(dk), _ext.ptr(dv), _ext.ptr(ws),
                                               B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin),
                                               float(hd ** -0.5), 2, ks, _ext.stream_ptr(dev)), "nd_attn_bwd_fused_ks")
-            return (dqkv,) + (None,) * 12
+            return (dqkv,) + (None,) * 13
         delta = torch.empty(B, nh, T, dtype=torch.float32, device=dev)
         _ext.check(L.nd_attn_bwd_pre(_ext.ptr(o), _ext.ptr(do), _ext.ptr(delta), B, nh, T, hd, nh * hd,
                                      _ext.stream_ptr(dev)), "nd_attn_bwd_pre")
@@ -149,7 +174,7 @@ class FlashAttnFn(torch.autograd.Function):
                                     _ext.ptr(delta), _ext.ptr(dqkv), _ext.ptr(dk), _ext.ptr(dv), _ext.ptr(ws),
                                     B, nh, nkv, T, hd, ld, nh * hd, _ext.ptr(cos), _ext.ptr(sin), float(hd ** -0.5), 2,
                                     ks, _ext.stream_ptr(dev)), "nd_attn_bwd_ks")
-        return (dqkv,) + (None,) * 12
+        return (dqkv,) + (None,) * 13
 
 
 def key_start(attention_mask: torch.Tensor) -> torch.Tensor:
@@ -217,7 +242,8 @@ def check_doc_bounds(doc_start: torch.Tensor, doc_end: torch.Tensor) -> None:
 
 def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T: int, nh: int, nkv: int,
               hd: int, inplace: bool = False, kstart: torch.Tensor = None, rotated: bool = False,
-              doc_bounds: Tuple[torch.Tensor, torch.Tensor] = None, window: int = None) -> torch.Tensor:
+              doc_bounds: Tuple[torch.Tensor, torch.Tensor] = None, window: int = None,
+              softcap: float = None) -> torch.Tensor:
     """Causal self-attention with RoPE; qkv [B*T, (nh+2nkv)*hd] -> [B*T, nh*hd].
 
     ``kstart`` (int32 [B], from :func:`key_start`) masks left padding: real queries (t >= kstart[b])
@@ -232,7 +258,12 @@ def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T
     ``window`` (None / 0 = off): sliding-window attention -- query q attends to keys
     max(kstart[b], q - window + 1) <= k <= q, the query itself counted (HF ``sliding_window``).  Composes with
     ``kstart``, not with ``doc_bounds``.  ``window >= T`` is no window: today's path, bit for bit.  The HIP path
-    has no windowed backward for T % 64 != 0 (forward only, e.g. prefill): a gradient there is refused up front."""
+    has no windowed backward for T % 64 != 0 (forward only, e.g. prefill): a gradient there is refused up front.
+    ``softcap`` (None / 0 = off: today's path, bit for bit): attention logit soft-capping -- the scores become
+    ``C tanh(scale q.k / C)`` before the mask and the softmax (HF Gemma 2 ``attn_logit_softcapping``).  Composes with
+    ``kstart``, ``doc_bounds`` and ``window``.  On the HIP path the capped backward exists for T % 64 == 0 only, like
+    the windowed one: a capped gradient at any other T is refused up front (the forward serves every T)."""
+    softcap = ref.check_attn_softcap(softcap)
     if rotated and not qkv.is_cuda:
         raise ValueError("rotated=True is a GPU-path contract (fused RoPE GEMM epilogue)")
     if window is not None and window < 0:
@@ -255,16 +286,26 @@ def attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, T
             if T % 64 and torch.is_grad_enabled() and qkv.requires_grad:
                 raise ValueError(f"sliding-window attention has no backward for T % 64 != 0 on the HIP path (T = {T}); "
                                  "run the forward under no_grad")
+        if softcap is not None:
+            if hd not in (32, 64, 128):
+                raise ValueError(f"soft-capped attention: head_dim {hd} not in (32, 64, 128)")
+            if T % 64 and torch.is_grad_enabled() and qkv.requires_grad:
+                raise ValueError(f"soft-capped attention has no backward for T % 64 != 0 on the HIP path (T = {T}); "
+                                 "run the forward under no_grad")
         x = qkv.contiguous()
         if not inplace and x.data_ptr() == qkv.data_ptr():
             x = x.clone()  # never rotate a caller-visible tensor
         if doc_bounds is not None:
             ds = ds.to(device=qkv.device, dtype=torch.int32).contiguous()
             de = de.to(device=qkv.device, dtype=torch.int32).contiguous()
+            if softcap is not None:
+                return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, None, bool(rotated), ds, de, None, softcap)
             return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, None, bool(rotated), ds, de)
         ks = kstart.to(device=qkv.device, dtype=torch.int32).contiguous() if kstart is not None else None
+        if softcap is not None:
+            return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, ks, bool(rotated), None, None, window, softcap)
         if window is not None:
             return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, ks, bool(rotated), None, None, window)
         return FlashAttnFn.apply(x, cos, sin, B, T, nh, nkv, hd, ks, bool(rotated))
     return ref.attention_block(qkv, cos, sin, B, T, nh, nkv, hd, use_sdpa=True, kstart=kstart, doc_bounds=doc_bounds,
-                               window=window)
+                               window=window, softcap=softcap)

@@ -62,6 +62,8 @@ class KVCache:
         # sliding window (None = off): a decode step sees keys max(kstart, pos - window + 1) .. pos.  The cache stays
         # static (s_max slots); only what a step reads shrinks
         self.window = int(getattr(c, "sliding_window", None) or 0) or None
+        # attention soft-cap (None = off): the decode scores are capped as the training kernels cap theirs
+        self.softcap = ref.check_attn_softcap(getattr(c, "attn_logit_softcapping", None))
         shape = (self.batch, self.nkv, self.s_max, self.hd)
         self.k = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(c.num_hidden_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(c.num_hidden_layers)]
@@ -124,11 +126,13 @@ def _check_window(window) -> Optional[int]:
 
 
 def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_ml, nh: int, nkv: int, hd: int,
-                       out: Optional[torch.Tensor] = None, window: Optional[int] = None) -> torch.Tensor:
-    """``nd_attn_decode`` (``window``: ``nd_attn_decode_win``) on raw tensors; every shape, dtype, contiguity and
+                       out: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                       softcap: Optional[float] = None) -> torch.Tensor:
+    """``nd_attn_decode`` (``window``: ``nd_attn_decode_win``; ``softcap``: ``nd_attn_decode_cap``) on raw tensors; every shape, dtype, contiguity and
     alignment the kernel relies on is checked here, before the launch.  The positions live on the device and are NOT
     checked (``KVCache`` keeps a host-side bound for that); the kernel itself ignores a position outside the cache."""
     window = _check_window(window)
+    softcap = ref.check_attn_softcap(softcap)
     if hd not in HEAD_DIMS:
         raise ValueError(f"decode attention: head_dim {hd} not in {HEAD_DIMS}")
     if nh < 1 or nkv < 1 or nh % nkv or nh // nkv > MAX_REP:
@@ -170,6 +174,13 @@ def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_
                     ("part_o", part_o), ("part_ml", part_ml)):
         if t.data_ptr() % 16:
             raise ValueError(f"decode attention: {name} must be 16-byte aligned")
+    if softcap is not None:
+        _ext.check(_ext.lib().nd_attn_decode_cap(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos),
+                                                 _ext.ptr(kstart), _ext.ptr(kcache), _ext.ptr(vcache), _ext.ptr(part_o),
+                                                 _ext.ptr(part_ml), _ext.ptr(out), B, nh, nkv, hd, s_max, qkv.stride(0),
+                                                 float(hd ** -0.5), min(window or 0, 2 ** 31 - 1), softcap,
+                                                 _ext.stream_ptr(qkv.device)), "nd_attn_decode_cap")
+        return out
     if window is not None:
         _ext.check(_ext.lib().nd_attn_decode_win(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos),
                                                  _ext.ptr(kstart), _ext.ptr(kcache), _ext.ptr(vcache), _ext.ptr(part_o),
@@ -185,9 +196,10 @@ def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_
 
 
 def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, nkv: int, hd: int,
-                           window: Optional[int] = None) -> torch.Tensor:
+                           window: Optional[int] = None, softcap: Optional[float] = None) -> torch.Tensor:
     """The PyTorch twin on raw tensors (any device / float dtype); same contract as ``attn_decode_launch``."""
     window = _check_window(window)
+    softcap = ref.check_attn_softcap(softcap)
     B, _, s_max, _ = kcache.shape
     q, k, v = qkv.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
     p = pos.long()
@@ -206,6 +218,12 @@ def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, 
     if nkv != nh:
         kk = kk.repeat_interleave(nh // nkv, dim=1)
         vv = vv.repeat_interleave(nh // nkv, dim=1)
+    if softcap is not None:  # SDPA cannot cap: a manual masked softmax in fp32
+        z = softcap * torch.tanh(torch.matmul(q.float(), kk.float().transpose(-1, -2)) * (hd ** -0.5 / softcap))
+        z = z.masked_fill(~mask, float("-inf"))
+        live = mask.any(-1, keepdim=True)
+        pr = torch.softmax(torch.where(live, z, torch.zeros_like(z)), dim=-1) * live
+        return torch.matmul(pr, vv.float()).to(qkv.dtype).reshape(B, nh * hd)
     o = F.scaled_dot_product_attention(q, kk, vv, attn_mask=mask)
     return o.reshape(B, nh * hd)
 
@@ -217,9 +235,10 @@ def attention_decode(qkv: torch.Tensor, cache: KVCache, layer: int, cos: torch.T
         if cache.part_o is None:
             cache.part_o, cache.part_ml = decode_workspace(cache.batch, cache.nh, cache.hd, cache.s_max, cache.device)
         return attn_decode_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.part_o,
-                                  cache.part_ml, cache.nh, cache.nkv, cache.hd, window=cache.window)
+                                  cache.part_ml, cache.nh, cache.nkv, cache.hd, window=cache.window,
+                                  softcap=cache.softcap)
     return attention_decode_torch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.nh,
-                                  cache.nkv, cache.hd, window=cache.window)
+                                  cache.nkv, cache.hd, window=cache.window, softcap=cache.softcap)
 
 
 def cache_fill(cache: KVCache, layer: int, qkv: torch.Tensor, B: int, T: int, cos=None, sin=None,

@@ -117,6 +117,17 @@ def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.T
 
 
 # ----------------------------------------------------------------------------- attention
+def check_attn_softcap(cap) -> Optional[float]:
+    """The attention soft-cap as a float, or None when off (None / 0); anything else that is not finite and > 0 is
+    refused."""
+    if cap is None or cap == 0:
+        return None
+    c = float(cap)
+    if not (c > 0 and math.isfinite(c)):
+        raise ValueError(f"attention soft-cap must be finite and > 0 (None / 0 = off), not {cap}")
+    return c
+
+
 def split_qkv(qkv: torch.Tensor, B: int, T: int, nh: int, nkv: int, hd: int):
     q, k, v = qkv.view(B, T, -1).split([nh * hd, nkv * hd, nkv * hd], dim=-1)
     q = q.reshape(B, T, nh, hd).transpose(1, 2)
@@ -174,12 +185,15 @@ def window_causal_mask(window: int, T: int, kstart: Optional[torch.Tensor] = Non
 
 def attention_block(qkv: torch.Tensor, cos, sin, B: int, T: int, nh: int, nkv: int, hd: int,
                     use_sdpa: bool = True, kstart: torch.Tensor = None, doc_bounds=None,
-                    window: Optional[int] = None) -> torch.Tensor:
+                    window: Optional[int] = None, softcap: Optional[float] = None) -> torch.Tensor:
     """qkv [B*T, (nh+2nkv)*hd] -> RoPE -> causal attention -> [B*T, nh*hd] (autograd-capable).
     ``kstart``: left-padding key start per sequence (see ``ops.attention.key_start``).
     ``doc_bounds``: (doc_start, doc_end) of a packed window (see ``ops.attention.doc_bounds``).
     ``window``: sliding window (None / 0 = off; composes with ``kstart``, not with ``doc_bounds``); a window of T or
-    more keys is the whole prefix and takes the un-windowed path."""
+    more keys is the whole prefix and takes the un-windowed path.
+    ``softcap`` (None / 0 = off): attention logit soft-capping, scores ``C tanh(scale q.k / C)`` before the mask and the
+    softmax (HF Gemma 2's order); composes with every mask.  A manual masked softmax in fp32: SDPA cannot cap."""
+    softcap = check_attn_softcap(softcap)
     if window is not None and window < 0:
         raise ValueError(f"sliding window must be >= 1 (None / 0 = off), not {window}")
     if window and doc_bounds is not None:
@@ -191,6 +205,24 @@ def attention_block(qkv: torch.Tensor, cos, sin, B: int, T: int, nh: int, nkv: i
     k = apply_rope(k, cos[:T], sin[:T])
     if kstart is not None and doc_bounds is not None:
         raise ValueError("kstart (left padding) and doc_bounds (packed documents) cannot be combined")
+    if softcap is not None:
+        t = torch.arange(T, device=qkv.device)
+        mask = (t[None, :] <= t[:, None]).view(1, 1, T, T)
+        if window is not None:
+            mask = window_causal_mask(window, T, kstart.to(qkv.device) if kstart is not None else None, qkv.device)
+        elif kstart is not None:
+            mask = padded_causal_mask(kstart.to(qkv.device), T)
+        elif doc_bounds is not None:
+            mask = doc_causal_mask(doc_bounds[0].to(qkv.device), T)
+        if nkv != nh:
+            k = k.repeat_interleave(nh // nkv, dim=1)
+            v = v.repeat_interleave(nh // nkv, dim=1)
+        z = softcap * torch.tanh(torch.matmul(q.float(), k.float().transpose(-1, -2)) * (hd ** -0.5 / softcap))
+        z = z.masked_fill(~mask, float("-inf"))
+        live = mask.any(-1, keepdim=True)  # a row with no visible key (a left-pad query) gives 0, as the kernels do
+        p = torch.softmax(torch.where(live, z, torch.zeros_like(z)), dim=-1) * live
+        o = torch.matmul(p, v.float()).to(qkv.dtype)
+        return o.transpose(1, 2).reshape(B * T, nh * hd)
     if kstart is not None or doc_bounds is not None or window is not None:
         if window is not None:
             mask = window_causal_mask(window, T, kstart.to(qkv.device) if kstart is not None else None, qkv.device)

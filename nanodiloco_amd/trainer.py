@@ -68,6 +68,10 @@ class TrainArgs:
                                    # lm-head CE kernels and wherever the model hands logits out (0 = off; the same as
                                    # "final_logit_softcapping": C in the model config).  A resumed checkpoint's
                                    # config.json carries it.  docs/DESIGN.md "Logit soft-capping"
+    attn_softcap: float = 0.0      # attention logit soft-capping: every layer's attention scores are
+                                   # C * tanh(scale q.k / C) before the mask and the softmax, inside the attention
+                                   # kernels (0 = off; the same as "attn_logit_softcapping": C in the model config).  A
+                                   # resumed checkpoint's config.json carries it.  docs/DESIGN.md "Attention soft-capping"
     qk_norm: bool = False          # QK-norm: a per-head RMSNorm of q and k before RoPE with one learnable [head_dim]
                                    # weight each per layer (Qwen3; docs/DESIGN.md "QK-norm").  Forces the model
                                    # config's `qk_norm` key on; a resumed checkpoint's config.json turns it on as well
@@ -226,6 +230,18 @@ def check_sliding_window(window, doc_mask: bool, data_kind: str, seq_length: int
             raise ValueError(f"--sliding-window on a GPU needs --seq-length to be a multiple of 64 (got {seq_length})")
 
 
+def check_attn_softcap(cap, data_kind: str, seq_length: int, on_gpu: bool, ops_backend: str = "auto") -> None:
+    """Refuse at start-up what the capped attention kernels cannot train: on the HIP path their backward exists for
+    whole 64-key tiles only, as the windowed one (see ``check_sliding_window``)."""
+    if not cap or not on_gpu or ops_backend == "torch":
+        return
+    if data_kind == "hf":
+        raise ValueError("--attn-softcap on a GPU needs fixed windows of a multiple of 64 tokens; --data hf pads its "
+                         "batches to multiples of 8 (use --ops torch, or packed data)")
+    if seq_length % 64:
+        raise ValueError(f"--attn-softcap on a GPU needs --seq-length to be a multiple of 64 (got {seq_length})")
+
+
 def _checkpoint_config(a: TrainArgs):
     """The LlamaConfig of the checkpoint this run resumes from (None: no resume, or no config.json there)."""
     if not a.resume:
@@ -262,6 +278,8 @@ class Trainer:
             raise ValueError(f"--z-loss must be a finite coefficient >= 0 (0 = off), got {a.z_loss}")
         if not 0.0 <= a.logit_softcap < float("inf"):
             raise ValueError(f"--logit-softcap must be a finite cap > 0 (0 = off), got {a.logit_softcap}")
+        if not 0.0 <= a.attn_softcap < float("inf"):
+            raise ValueError(f"--attn-softcap must be a finite cap > 0 (0 = off), got {a.attn_softcap}")
         if a.comm_rank:
             if not 1 <= a.comm_rank <= 32:
                 raise ValueError(f"--comm-rank must be in [1, 32] columns per factor (0 = off), got {a.comm_rank}")
@@ -319,6 +337,16 @@ class Trainer:
         cap = a.logit_softcap or ck_cap
         if cap and float(cap) != float(self.llama_config.final_logit_softcapping or 0.0):
             self.llama_config = dataclasses.replace(self.llama_config, final_logit_softcapping=float(cap))
+        ck_acap = (ck.attn_logit_softcapping or 0.0) if ck is not None else 0.0
+        if ck is not None and a.attn_softcap and float(a.attn_softcap) != float(ck_acap):
+            raise ValueError(f"--attn-softcap {a.attn_softcap:g} differs from the checkpoint's attn_logit_softcapping "
+                             f"({ck_acap or 'off'}): a resumed run continues the model its config.json describes "
+                             "(drop the flag)")
+        acap = a.attn_softcap or ck_acap
+        if acap and float(acap) != float(self.llama_config.attn_logit_softcapping or 0.0):
+            self.llama_config = dataclasses.replace(self.llama_config, attn_logit_softcapping=float(acap))
+        check_attn_softcap(self.llama_config.attn_logit_softcapping, _resolve_data_kind(a), a.seq_length,
+                           e.device.type == "cuda", a.ops)
         if str(a.per_device_batch_size).lower() == "auto":
             a.per_device_batch_size = auto_micro_batch(self.llama_config, a.seq_length, a.batch_size, e.device)
         a.per_device_batch_size = int(a.per_device_batch_size)
@@ -575,6 +603,8 @@ class Trainer:
             extra["sliding_window"] = self.llama_config.sliding_window
         if self.llama_config.final_logit_softcapping:  # likewise: no key, no cap
             extra["final_logit_softcapping"] = self.llama_config.final_logit_softcapping
+        if self.llama_config.attn_logit_softcapping:
+            extra["attn_logit_softcapping"] = self.llama_config.attn_logit_softcapping
         save_checkpoint(self.args.checkpoint_dir, self.model, self.diloco, self.env, step, data_state=ds,
                         extra=extra)
 
