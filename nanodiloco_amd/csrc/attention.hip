@@ -33,63 +33,8 @@
 
 using namespace nd;
 
-__device__ __forceinline__ bf16x8 cat4(sv4 a, sv4 b) {
-  bf16x8 r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
-  r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-  return r;
-}
-
-// Pack accumulator registers 8s..8s+7 into a bf16 MFMA operand fragment.
-__device__ __forceinline__ bf16x8 pack_frag(const f32x16& x, int s) {
-  u32x4 u;
-  u[0] = pack2(x[8 * s + 0], x[8 * s + 1]);
-  u[1] = pack2(x[8 * s + 2], x[8 * s + 3]);
-  u[2] = pack2(x[8 * s + 4], x[8 * s + 5]);
-  u[3] = pack2(x[8 * s + 6], x[8 * s + 7]);
-  return __builtin_bit_cast(bf16x8, u);
-}
-
 __device__ __forceinline__ bf16x8 load16(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
 __device__ __forceinline__ bf16x8 zero8() { return bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
-
-// Element offset of (row, col) inside an XOR-swizzled [rows][HD] bf16 LDS tile (16-B chunks).
-// The XOR key s(row) must keep BOTH access kinds conflict-free:
-//  * row reads (ds_read_b128): 16 consecutive rows at one logical chunk -> 16 distinct bank slots;
-//  * transposed reads (ds_read_b64_tr_b16): a 32-lane half reads rows r0..r0+3 (r0 % 4 == 0), 64 B
-//    each, so rows that share a bank row must differ in the chunk bit that picks the 64-B half.
-// HD=64 (two 128-B rows per 256-B bank row): s = bitreverse3((row >> 1) & 7)  [rows r0, r0+2 differ in bit 2]
-// HD=128 (one row per bank row):             s = ((row & 3) << 2) | ((row >> 2) & 3)
-// HD=32 (four 64-B rows per bank row):        s = (row >> 2) & 3
-template <int HD>
-__device__ __forceinline__ int soff(int row, int col) {
-  int key;
-  if constexpr (HD == 64) {
-    const int u = (row >> 1) & 7;
-    key = ((u & 1) << 2) | (u & 2) | ((u >> 2) & 1);
-  } else if constexpr (HD == 128) {
-    key = ((row & 3) << 2) | ((row >> 2) & 3);
-  } else {
-    key = (row >> 2) & 3;
-  }
-  const int ch = (col >> 3) ^ key;
-  return row * HD + ch * 8 + (col & 7);
-}
-
-// A/B fragment with rows on the lanes: row `row`, k-step t, lane half h -> cols 16t + 8h .. +7
-template <int HD>
-__device__ __forceinline__ bf16x8 row_frag(const bf16_t* tile, int row, int t, int h) {
-  return *reinterpret_cast<const bf16x8*>(&tile[soff<HD>(row, 16 * t + 8 * h)]);
-}
-
-// Transposed fragment for the permuted-k operand: rows r0 + 16s + 8(j>>2) + 4h + (j&3), column
-// c0 + (lane & 31).  (g, i) = (lane >> 4, lane & 15).
-template <int HD>
-__device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int rbase, int cbase, int g, int i) {
-  const int row = rbase + 4 * (g >> 1) + (i >> 2);
-  const int col = cbase + 16 * (g & 1) + 4 * (i & 3);
-  return cat4(tr_read(&tile[soff<HD>(row, col)]), tr_read(&tile[soff<HD>(row + 8, col)]));
-}
 
 // Rotate 8 (x1, x2) pairs held as two bf16x8 chunks: x1' = x1 c - x2 s, x2' = x2 c + x1 s
 // (sgn = -1 applies the inverse rotation).  fp32 math, one rounding, same as nd_rope_inplace.

@@ -66,6 +66,8 @@ def _run(cmd):
 # v_pk_fma_f32) issued beside MFMAs costs more than two scalar ops (MI355X_MICROARCH price list).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # no v_pk_{add,mul,fma}_f32 at all
 FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"],
+              # attn_extend.hip: the multi-token KV-cache attention, softmax VALU beside MFMAs like attention.hip
+              "attn_extend.hip": ["-fno-slp-vectorize"],
               # the capped attention kernels: the templates of attention.hip / attn_decode.hip in objects of their own
               "attn_softcap.hip": ["-fno-slp-vectorize"] + _NO_PK_F32,
               "attn_decode_cap.hip": _NO_PK_F32,

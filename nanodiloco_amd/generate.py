@@ -3,7 +3,7 @@
     python -m nanodiloco_amd.generate --checkpoint DIR (--prompt-ids "1,2,3" ... | --prompt-file F | --prompt "text" ...)
         [--llama-config-file F] [--max-new-tokens 32] [--temperature 0] [--top-k 0] [--top-p 1.0] [--seed 0]
         [--dtype auto] [--residual-dtype auto] [--device auto] [--hip-graph auto|on|off]
-        [--tokenizer PATH]
+        [--tokenizer PATH] [--prefill-chunk 0]
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``), the config comes from ``--llama-config-file`` or the checkpoint's ``config.json`` -- as
@@ -13,7 +13,8 @@ of ids per line.  The prompts form one left-padded batch.  Output: one JSON line
 ``token_ids``: prompt + continuation, ``new_tokens``; with a tokenizer also ``text``), then one line with
 ``prefill_s``, ``decode_s`` and ``decode_tokens_per_s``.  ``--tokenizer PATH`` (optional) encodes ``--prompt`` and decodes
 the result through ``AutoTokenizer.from_pretrained(PATH, local_files_only=True)``: nothing is ever fetched; without
-it only ids are accepted.
+it only ids are accepted.  ``--prefill-chunk N`` (N > 0) prefills the prompt in pieces of N tokens through the
+multi-token KV-cache attention (``model.extend``) instead of one whole-prompt forward.
 """
 from __future__ import annotations
 
@@ -44,6 +45,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--residual-dtype", default="auto", help="auto | fp32 | bf16")
     p.add_argument("--device", default="auto", help="auto | cpu | cuda")
     p.add_argument("--hip-graph", default="auto", choices=["auto", "on", "off"])
+    p.add_argument("--prefill-chunk", type=int, default=0,
+                   help="prefill the prompt in pieces of N tokens through model.extend (0: one whole-prompt forward)")
     return p
 
 
@@ -99,7 +102,7 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
         mask[i, T - len(p):] = 1
     ids, mask = ids.to(device), mask.to(device)
     kw = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed,
-              hip_graph={"auto": "auto", "on": True, "off": False}[a.hip_graph])
+              hip_graph={"auto": "auto", "on": True, "off": False}[a.hip_graph], prefill_chunk=a.prefill_chunk)
     amask = mask if len(prompts) > 1 else None
 
     def sync():

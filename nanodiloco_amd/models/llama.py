@@ -308,17 +308,26 @@ class LlamaForCausalLM:
     def new_cache(self, batch: int, s_max: int):
         return ops.KVCache(self.config, batch, s_max, self.device, self.compute_dtype)
 
-    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], cache) -> torch.Tensor:
+    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], cache,
+                chunk: int = 0) -> torch.Tensor:
         """The existing forward on a (left-padded) prompt batch [B, T], every layer's k|v into ``cache`` slots
         0 .. T-1, ``pos = T``, ``kstart = ops.key_start(attention_mask)``.  Returns the last position's logits [B, V]
         (fp32).  Positions are slot indices, the training path's convention under left padding (scores depend on
-        q - k only)."""
+        q - k only).  ``chunk`` = N > 0: the prompt goes through ``extend`` in pieces of N tokens instead (bounded
+        activation memory; the same cache contract)."""
         B, T = input_ids.shape
         if self.doc_mask:
             raise ValueError("generation runs on single documents: build the model without doc_mask")
         if B != cache.batch or T > cache.s_max:
             raise ValueError(f"a [{B}, {T}] prompt does not fit a KV cache of batch {cache.batch}, "
                              f"s_max {cache.s_max}")
+        if chunk < 0:
+            raise ValueError("prefill: chunk must be >= 0 (0 = the whole prompt in one forward)")
+        if chunk > 0:
+            cache.set_positions([0] * B, ops.key_start(attention_mask).tolist() if attention_mask is not None else None)
+            for t0 in range(0, T, chunk):
+                logits = self.extend(input_ids[:, t0:t0 + chunk], cache, last_only=True)
+            return logits
         with self._inference():
             y = self.hidden_states(input_ids, attention_mask, cache=cache)
             cache.pos.fill_(T)
@@ -365,17 +374,55 @@ class LlamaForCausalLM:
         cache.advance(device_side=False)
         return logits
 
+    def extend(self, input_ids: torch.Tensor, cache, last_only: bool = False) -> torch.Tensor:
+        """Append L tokens per sequence (``input_ids`` [B, L], token i at slot ``cache.pos + i``) to a cache that may
+        already hold keys: fp32 logits [B, L, V], or [B, V] of the last token with ``last_only``.  The decode step's
+        layer loop over B*L rows with ``ops.attention_extend`` (every weight streamed once for the L tokens), then
+        ``cache.advance(L)``."""
+        c = self.config
+        if self.doc_mask:
+            raise ValueError("generation runs on single documents: build the model without doc_mask")
+        if input_ids.dim() != 2 or input_ids.shape[0] != cache.batch or input_ids.shape[1] < 1:
+            raise ValueError(f"extend needs input_ids [B = {cache.batch}, L >= 1], not {tuple(input_ids.shape)}")
+        B, T = input_ids.shape
+        cache.check_room(T)
+        cdt, eps = self.compute_dtype, c.rms_norm_eps
+        with self._inference():
+            cos, sin = ops.rope_cache(cache.s_max, c.head_dim, c.rope_theta, c.rope_scaling, self.device)
+            h = ops.embedding(input_ids, self._m("model.embed_tokens.weight"), None, out_dtype=self.residual_dtype)
+            y, h = ops.rmsnorm_res(h, self._m("model.layers.0.input_layernorm.weight"), None, eps, cdt)
+            L = c.num_hidden_layers
+            for i in range(L):
+                p = f"model.layers.{i}."
+                qkv = ops.mm_nt(y, self._fused(self._qkv_names[i], "shadow"))
+                if c.qk_norm:  # in place on the new rows; the extend kernel rotates what it finds there
+                    ops.qk_norm(qkv, self._m(p + "self_attn.q_norm.weight"), self._m(p + "self_attn.k_norm.weight"),
+                                c.num_attention_heads, c.num_key_value_heads, c.head_dim, eps)
+                o = ops.attention_extend(qkv, cache, i, cos, sin, T)
+                a = ops.mm_nt(o, self._w(p + "self_attn.o_proj.weight"))
+                y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"), None, eps, cdt)
+                gu = ops.mm_nt(y, self._fused(self._gu_names[i], "shadow"))
+                m = ops.mm_nt(ops.swiglu(gu), self._w(p + "mlp.down_proj.weight"))
+                nxt = f"model.layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "model.norm.weight"
+                y, h = ops.add_rmsnorm(h, m, self._m(nxt), None, eps, cdt)
+            if last_only:
+                y = y.view(B, T, -1)[:, -1].contiguous()
+            logits = self._capped(ops.mm_nt(y, self._w(self._lm_name())).float())
+        cache.advance(T)
+        return logits if last_only else logits.view(B, T, -1)
+
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                  max_new_tokens: int = 32, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  eos_token_id=_CONFIG, pad_token_id=_CONFIG, seed: int = 0, use_cache: bool = True,
-                 hip_graph="auto", return_logits: bool = False):
+                 hip_graph="auto", return_logits: bool = False, prefill_chunk: int = 0):
         """Continue a (left-padded) prompt batch ``input_ids`` [B, T]; returns the token ids [B, T + n], n <=
         ``max_new_tokens`` (generation ends early once every row has produced ``eos_token_id``; a finished row is
         filled with ``pad_token_id``).  ``temperature`` 0 is greedy; otherwise ``filter_logits`` (top-k, top-p) and
         ``torch.multinomial`` with a generator seeded by ``seed``.  ``use_cache=False`` recomputes the whole prefix
         per token (the check and the timing baseline).  ``hip_graph``: True / False / "auto" (on for a GPU, non-fp8
         model on the HIP path): the decode step is captured once after two eager steps and replayed.
-        ``return_logits``: also the fp32 logits [B, n, V] every token was drawn from."""
+        ``return_logits``: also the fp32 logits [B, n, V] every token was drawn from.  ``prefill_chunk`` = N > 0 (with
+        ``use_cache``): the prompt is prefilled through ``extend`` in pieces of N tokens."""
         c = self.config
         eos = c.eos_token_id if eos_token_id is _CONFIG else eos_token_id
         pad = pad_token_id
@@ -402,7 +449,7 @@ class LlamaForCausalLM:
             raise ValueError("hip_graph needs use_cache=True on a GPU")
         if use_cache:
             cache = self.new_cache(B, T + n - 1)  # the last token drawn is never fed back
-            logits = self.prefill(input_ids, attention_mask, cache)
+            logits = self.prefill(input_ids, attention_mask, cache, chunk=int(prefill_chunk))
             step = functools.partial(self.decode_step, cache=cache)
             if hip_graph:
                 from ..utils.graphs import GraphedDecodeStep

@@ -168,6 +168,10 @@ def _declare(L: ctypes.CDLL):
         "nd_attn_decode_win": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, I, P],
         "nd_attn_decode_cap": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, I, F, P],  # ..., window, cap, stream
         "nd_attn_decode_split": [],
+        # multi-token attention against a KV cache on MFMA: append, split-KV tiles, combine (csrc/attn_extend.hip)
+        # ..., o, B, L, nh, nkv, hd, S_max, ld, scale, window (0 = none), cap (0 = none), stream
+        "nd_attn_extend": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L64, F, I, F, P],
+        "nd_attn_extend_qblock": [],
         # mlp
         "nd_swiglu_fwd": [P, P, I, L64, I, P],
         "nd_swiglu_bwd": [P, P, P, I, L64, I, P],

@@ -16,6 +16,14 @@ CPU, or under ``--ops torch``, a PyTorch twin with the same contract runs (``ref
 indexed slot write, masked SDPA over the whole cache); it is also the timing baseline.  The twin multiplies masked
 probabilities (exact zeros) with whatever the unused slots hold, so it needs finite slots: ``KVCache`` starts zeroed.
 
+``attention_extend(qkv, cache, layer, cos, sin, L)`` is the multi-token step: ``qkv`` [B*L, (nh + 2 nkv) hd] holds L new
+tokens per sequence (row ``b*L + i`` at slot and RoPE position ``pos[b] + i``); they are rotated, appended to slots
+``pos .. pos+L-1`` and every query row ``i`` attends keys ``max(kstart, pos+i-window+1) .. pos+i``.  HIP path
+(``csrc/attn_extend.hip``, ``nd_attn_extend``): an append launch, then per block of at most ``extend_qblock()`` queries
+an MFMA split-KV attention launch over the decode kernel's key partition and a combine launch; a row's bits depend on
+its query, its key range and the partition alone (not on L, B or how a run of tokens was cut into calls).  ``pos`` is
+not advanced: ``cache.advance(L)``.
+
 ``cache_fill`` is the prefill side: it copies the k|v columns of the training path's packed q|k|v buffer into slots
 ``0 .. T-1``.
 """
@@ -46,6 +54,18 @@ def decode_workspace(B: int, nh: int, hd: int, s_max: int, device, split: Option
             torch.empty(B * nh * nchunks, 2, dtype=torch.float32, device=device))
 
 
+def extend_qblock() -> int:
+    """Queries per attention launch of ``nd_attn_extend`` (compile-time ``QBLOCK``): what its workspace is sized for."""
+    return int(_ext.lib().nd_attn_extend_qblock())
+
+
+def extend_workspace(B: int, nh: int, hd: int, s_max: int, device):
+    """(part_o [B * nh * nchunks * qblock, hd], part_ml [.., 2]) fp32 for ``nd_attn_extend``."""
+    n = B * nh * ((s_max + decode_split() - 1) // decode_split()) * extend_qblock()
+    return (torch.empty(n, hd, dtype=torch.float32, device=device),
+            torch.empty(n, 2, dtype=torch.float32, device=device))
+
+
 class KVCache:
     def __init__(self, config, batch: int, s_max: int, device, dtype: torch.dtype):
         c = config
@@ -74,6 +94,7 @@ class KVCache:
         self.part_o = self.part_ml = None
         if self.device.type == "cuda" and _ext.get_backend() != "torch":
             self.part_o, self.part_ml = decode_workspace(self.batch, self.nh, self.hd, self.s_max, self.device)
+        self.ext_o = self.ext_ml = None  # attention_extend's workspace, allocated at its first use
 
     def set_positions(self, pos, kstart=None) -> None:
         """Set ``pos`` (and ``kstart``; None: 0) from host sequences or tensors.  A setup call: a tensor ``pos`` is
@@ -94,9 +115,9 @@ class KVCache:
                 raise ValueError(f"kstart must have {self.batch} non-negative entries")
             self.kstart.copy_(ks)
 
-    def check_room(self) -> None:
-        if self.max_pos >= self.s_max:
-            raise ValueError(f"the KV cache is full: position {self.max_pos} with s_max = {self.s_max}")
+    def check_room(self, n: int = 1) -> None:
+        if self.max_pos + n > self.s_max:
+            raise ValueError(f"the KV cache is full: position {self.max_pos} + {n} with s_max = {self.s_max}")
 
     def advance(self, n: int = 1, device_side: bool = True) -> None:
         """One step done: ``pos += n`` on the device (no host sync).  ``device_side=False`` moves only the host-side
@@ -238,6 +259,121 @@ def attention_decode(qkv: torch.Tensor, cache: KVCache, layer: int, cos: torch.T
                                   cache.part_ml, cache.nh, cache.nkv, cache.hd, window=cache.window,
                                   softcap=cache.softcap)
     return attention_decode_torch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.nh,
+                                  cache.nkv, cache.hd, window=cache.window, softcap=cache.softcap)
+
+
+def attn_extend_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_ml, L: int, nh: int, nkv: int, hd: int,
+                       out: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                       softcap: Optional[float] = None) -> torch.Tensor:
+    """``nd_attn_extend`` on raw tensors: L new tokens per sequence, ``qkv`` [B*L, (nh + 2 nkv) hd] (overwritten: q and
+    k rotated in place).  Every shape, dtype, contiguity and alignment the kernels rely on is checked here, before the
+    launch; the device positions are not (the kernels ignore a sequence whose L slots do not fit)."""
+    window = _check_window(window)
+    softcap = ref.check_attn_softcap(softcap)
+    if hd not in HEAD_DIMS:
+        raise ValueError(f"extend attention: head_dim {hd} not in {HEAD_DIMS}")
+    if nh < 1 or nkv < 1 or nh % nkv or nh // nkv > MAX_REP:
+        raise ValueError(f"extend attention: nh = {nh}, nkv = {nkv}: need nh % nkv == 0 and nh / nkv <= {MAX_REP}")
+    if kcache.dim() != 4 or kcache.shape != vcache.shape or kcache.shape[1] != nkv or kcache.shape[3] != hd:
+        raise ValueError("extend attention: the caches must be [B, nkv, S_max, hd]")
+    B, _, s_max, _ = kcache.shape
+    if B < 1 or s_max < 1:
+        raise ValueError("extend attention: empty cache")
+    if L < 1 or L > s_max:
+        raise ValueError(f"extend attention: L = {L} new tokens outside [1, s_max = {s_max}]")
+    W = (nh + 2 * nkv) * hd
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B * L, W):
+        raise ValueError(f"extend attention: qkv must be [{B * L}, {W}]")
+    for name, t in (("qkv", qkv), ("kcache", kcache), ("vcache", vcache)):
+        if t.dtype != torch.bfloat16 or not t.is_cuda:
+            raise ValueError(f"extend attention: {name} must be a bf16 GPU tensor")
+    if qkv.stride(1) != 1 or qkv.stride(0) < W or qkv.stride(0) % 8:
+        raise ValueError("extend attention: qkv rows must be contiguous with a stride that is a multiple of 8")
+    if not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError("extend attention: the caches must be contiguous")
+    for name, t in (("cos", cos), ("sin", sin)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != hd \
+                or t.shape[0] < s_max:
+            raise ValueError(f"extend attention: {name} must be a contiguous fp32 [>= {s_max}, {hd}] GPU table")
+    for name, t in (("pos", pos), ("kstart", kstart)):
+        if t is None and name == "kstart":
+            continue
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() != B:
+            raise ValueError(f"extend attention: {name} must be a contiguous int32 [{B}] GPU tensor")
+    need = B * nh * ((s_max + decode_split() - 1) // decode_split()) * min(L, extend_qblock())
+    for name, t, cols in (("part_o", part_o, hd), ("part_ml", part_ml, 2)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < need * cols:
+            raise ValueError(f"extend attention: {name} must be a contiguous fp32 workspace of {need * cols}")
+    if out is None:
+        out = torch.empty(B * L, nh * hd, dtype=torch.bfloat16, device=qkv.device)
+    elif out.dtype != torch.bfloat16 or not out.is_cuda or not out.is_contiguous() \
+            or tuple(out.shape) != (B * L, nh * hd):
+        raise ValueError(f"extend attention: out must be a contiguous bf16 [{B * L}, {nh * hd}] GPU tensor")
+    for name, t in (("qkv", qkv), ("cos", cos), ("sin", sin), ("kcache", kcache), ("vcache", vcache),
+                    ("part_o", part_o), ("part_ml", part_ml)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"extend attention: {name} must be 16-byte aligned")
+    _ext.check(_ext.lib().nd_attn_extend(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos), _ext.ptr(kstart),
+                                         _ext.ptr(kcache), _ext.ptr(vcache), _ext.ptr(part_o), _ext.ptr(part_ml),
+                                         _ext.ptr(out), B, L, nh, nkv, hd, s_max, qkv.stride(0), float(hd ** -0.5),
+                                         min(window or 0, 2 ** 31 - 1), float(softcap or 0.0),
+                                         _ext.stream_ptr(qkv.device)), "nd_attn_extend")
+    return out
+
+
+def attention_extend_torch(qkv, cos, sin, pos, kstart, kcache, vcache, L: int, nh: int, nkv: int, hd: int,
+                           window: Optional[int] = None, softcap: Optional[float] = None) -> torch.Tensor:
+    """The PyTorch twin on raw tensors (any device / float dtype); same contract as ``attn_extend_launch`` except that
+    ``qkv`` is left alone: rotation at ``pos + i``, slot writes by index, a masked fp32 softmax over the whole cache."""
+    window = _check_window(window)
+    softcap = ref.check_attn_softcap(softcap)
+    B, _, s_max, _ = kcache.shape
+    q, k, v = qkv.view(B, L, -1).split([nh * hd, nkv * hd, nkv * hd], dim=-1)
+    slot = pos.long().view(B, 1) + torch.arange(L, device=qkv.device)  # [B, L]
+    c, s = cos[slot].view(B, 1, L, hd), sin[slot].view(B, 1, L, hd)  # each token's own table row
+    q = ref.apply_rope(q.reshape(B, L, nh, hd).transpose(1, 2), c, s)
+    k = ref.apply_rope(k.reshape(B, L, nkv, hd).transpose(1, 2), c, s)
+    rows = torch.arange(B, device=qkv.device).view(B, 1)
+    kcache[rows, :, slot] = k.transpose(1, 2).to(kcache.dtype)  # indexed [B, L, nkv, hd]
+    vcache[rows, :, slot] = v.reshape(B, L, nkv, hd).to(vcache.dtype)
+    t = torch.arange(s_max, device=qkv.device)
+    lo = kstart.long().view(B, 1) if kstart is not None else torch.zeros(B, 1, dtype=torch.long, device=qkv.device)
+    lo = lo.expand(B, L)
+    if window is not None:
+        lo = torch.maximum(lo, slot - window + 1)
+    mask = ((t >= lo[..., None]) & (t <= slot[..., None])).view(B, 1, L, s_max)
+    kk, vv = kcache, vcache
+    if nkv != nh:
+        kk = kk.repeat_interleave(nh // nkv, dim=1)
+        vv = vv.repeat_interleave(nh // nkv, dim=1)
+    z = torch.matmul(q.float(), kk.float().transpose(-1, -2)) * hd ** -0.5
+    if softcap is not None:
+        z = softcap * torch.tanh(z / softcap)
+    z = z.masked_fill(~mask, float("-inf"))
+    live = mask.any(-1, keepdim=True)  # a pad query (slot < kstart) has no key: zeros, as the kernels
+    pr = torch.softmax(torch.where(live, z, torch.zeros_like(z)), dim=-1) * mask
+    o = torch.matmul(pr, vv.float()).to(qkv.dtype)
+    return o.transpose(1, 2).reshape(B * L, nh * hd)
+
+
+def attention_extend(qkv: torch.Tensor, cache: KVCache, layer: int, cos: torch.Tensor, sin: torch.Tensor,
+                     L: int) -> torch.Tensor:
+    """L new tokens per sequence through layer ``layer``; see the module doc.  Returns o [B*L, nh * hd]."""
+    W = (cache.nh + 2 * cache.nkv) * cache.hd
+    if L < 1 or qkv.dim() != 2 or tuple(qkv.shape) != (cache.batch * L, W):
+        raise ValueError(f"qkv must be [B*L, (nh + 2 nkv) hd] = [{cache.batch * L}, {W}], not {tuple(qkv.shape)}")
+    if not 0 <= layer < len(cache.k):
+        raise ValueError(f"layer {layer} outside the cache's {len(cache.k)} layers")
+    if cos.shape[0] < cache.s_max or cos.shape[1] != cache.hd or cos.shape != sin.shape:
+        raise ValueError(f"the RoPE tables must be [>= s_max = {cache.s_max}, hd = {cache.hd}]")
+    cache.check_room(L)
+    if _ext.use_hip(qkv):
+        if cache.ext_o is None:
+            cache.ext_o, cache.ext_ml = extend_workspace(cache.batch, cache.nh, cache.hd, cache.s_max, cache.device)
+        return attn_extend_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.ext_o,
+                                  cache.ext_ml, L, cache.nh, cache.nkv, cache.hd, window=cache.window,
+                                  softcap=cache.softcap)
+    return attention_extend_torch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], L, cache.nh,
                                   cache.nkv, cache.hd, window=cache.window, softcap=cache.softcap)
 
 
