@@ -43,10 +43,12 @@ using namespace nd;
 
 namespace {
 
+#ifndef ND_DECODE_KERNELS_ONLY  // attn_kv8.hip includes this file after attn_decode.hip, which has these two
 constexpr int SPLIT = 128;   // keys per workgroup: the decode kernel's partition (nd_attn_decode_split)
+constexpr float LOG2E = 1.4426950408889634f;
+#endif
 constexpr int QBLOCK = 64;   // queries per attention / combine launch (the workspace is sized for it)
 constexpr int XW = 4;        // waves = 32-row tiles per workgroup
-constexpr float LOG2E = 1.4426950408889634f;
 
 // rope.hip's rotation of 8 elements x (first half) and y (second half, element + hd/2), as that kernel compiles:
 // x' = fma(x, c, -(y * s)), y' = fma(y, c, x * s), rounded once to bf16 (attn_decode.hip's rope8)
@@ -107,23 +109,62 @@ attn_extend_append(bf16_t* __restrict__ qkv, const float* __restrict__ cosT, con
   }
 }
 
+// Stages keys [c0, c0 + SPLIT) of one (sequence, kv head) -- `row0` is its first cache row -- as swizzled LDS tiles:
+// slots [glo, ghi] are loaded, the rest of the tile is zero.  All 64 * XW threads; the caller's barrier follows.
+template <int HD>
+__device__ __forceinline__ void stage_chunk(const bf16_t* kcache, const bf16_t* vcache, bf16_t* Ks, bf16_t* Vs,
+                                            int64_t row0, int c0, int glo, int ghi) {
+  constexpr int CPR = HD / 8;
+  constexpr int NST = SPLIT * CPR / (64 * XW);  // 16-B pieces per thread and operand
+  const bf16_t* kc = kcache + row0 * HD;
+  const bf16_t* vc = vcache + row0 * HD;
+  uint4 kr[NST], vr[NST];
+#pragma unroll
+  for (int it = 0; it < NST; ++it) {
+    const int idx = threadIdx.x + it * (64 * XW);
+    const int key = c0 + idx / CPR, ch = idx % CPR;
+    kr[it] = make_uint4(0, 0, 0, 0);
+    vr[it] = make_uint4(0, 0, 0, 0);
+    if (key >= glo && key <= ghi) {
+      kr[it] = *reinterpret_cast<const uint4*>(kc + (int64_t)key * HD + ch * 8);
+      vr[it] = *reinterpret_cast<const uint4*>(vc + (int64_t)key * HD + ch * 8);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NST; ++it) {
+    const int idx = threadIdx.x + it * (64 * XW);
+    const int o = soff<HD>(idx / CPR, (idx % CPR) * 8);
+    *reinterpret_cast<uint4*>(&Ks[o]) = kr[it];
+    *reinterpret_cast<uint4*>(&Vs[o]) = vr[it];
+  }
+}
+
+// An fp8 cache operand (docs/DESIGN.md "fp8 KV cache"): e4m3 codes [B, nkv, S_max, hd] and one int8 exponent per row.
+// Its staging -- codes and exponents to the exact bf16 value code * 2^e, the same tiles -- is in attn_kv8.hip.
+struct Kv8 {
+  const uint8_t* codes;
+  const int8_t* exps;
+};
+template <int HD>
+__device__ __forceinline__ void stage_chunk(Kv8 kcache, Kv8 vcache, bf16_t* Ks, bf16_t* Vs, int64_t row0, int c0,
+                                            int glo, int ghi);
+
 // The geometry of one attention / combine launch: queries off .. off + Lb - 1 of the L new tokens.
 struct Block {
   int L, off, Lb;
 };
 
 // CA: empty, or one CapArgs: the scores become C log2(e) tanh(q.k scale / C), and `scale2` is then the plain scale
-// (as attn_decode_kernel).
-template <int HD, class... CA>
+// (as attn_decode_kernel).  KC: the cache operand, const bf16_t* or Kv8 -- only stage_chunk looks at it.
+template <int HD, class KC, class... CA>
 __global__ void __launch_bounds__(64 * XW)
 attn_extend_kernel(const bf16_t* __restrict__ qkv, const int* __restrict__ pos, const int* __restrict__ kstart,
-                   const bf16_t* __restrict__ kcache, const bf16_t* __restrict__ vcache, float* __restrict__ part_o,
+                   KC kcache, KC vcache, float* __restrict__ part_o,
                    float* __restrict__ part_ml, int nkv, int rep, int row_tiles, int S_max, int64_t ld, float scale2,
                    int window, Block blk, CA... ca) {
   constexpr bool CAP = has_cap<CA...>;
   static_assert(sizeof...(CA) == (CAP ? 1 : 0), "at most one trailing argument, a CapArgs");
-  constexpr int NT = HD / 16, NO = HD / 32, CPR = HD / 8;
-  constexpr int NST = SPLIT * CPR / (64 * XW);  // 16-B pieces per thread and operand
+  constexpr int NT = HD / 16, NO = HD / 32;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[SPLIT * HD];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[SPLIT * HD];
 
@@ -148,29 +189,7 @@ attn_extend_kernel(const bf16_t* __restrict__ qkv, const int* __restrict__ pos, 
   }
 
   // ---- stage the chunk: slots [glo, ghi] (inside [kstart, pos + L - 1], below S_max) are loaded, the rest is zero
-  {
-    const bf16_t* kc = kcache + (int64_t)(b * nkv + g) * S_max * HD;
-    const bf16_t* vc = vcache + (int64_t)(b * nkv + g) * S_max * HD;
-    uint4 kr[NST], vr[NST];
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int idx = threadIdx.x + it * (64 * XW);
-      const int key = c0 + idx / CPR, ch = idx % CPR;
-      kr[it] = make_uint4(0, 0, 0, 0);
-      vr[it] = make_uint4(0, 0, 0, 0);
-      if (key >= glo && key <= ghi) {
-        kr[it] = *reinterpret_cast<const uint4*>(kc + (int64_t)key * HD + ch * 8);
-        vr[it] = *reinterpret_cast<const uint4*>(vc + (int64_t)key * HD + ch * 8);
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int idx = threadIdx.x + it * (64 * XW);
-      const int o = soff<HD>(idx / CPR, (idx % CPR) * 8);
-      *reinterpret_cast<uint4*>(&Ks[o]) = kr[it];
-      *reinterpret_cast<uint4*>(&Vs[o]) = vr[it];
-    }
-  }
+  stage_chunk<HD>(kcache, vcache, Ks, Vs, (int64_t)(b * nkv + g) * S_max, c0, glo, ghi);
 
   // ---- this wave's tile: query row on the lane (both halves of the wave hold the same 32 rows)
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -301,13 +320,13 @@ __global__ void attn_extend_combine(const float* __restrict__ part_o, const floa
   o[(((int64_t)b * blk.L + ti) * nh + head) * hd + d] = f2bf(Lsum > 0.f ? O / Lsum : 0.f);
 }
 
-template <int HD, class... CA>
-int launch_block(const bf16_t* qkv, const int* pos, const int* kstart, const bf16_t* kc, const bf16_t* vc,
+template <int HD, class KC, class... CA>
+int launch_block(const bf16_t* qkv, const int* pos, const int* kstart, KC kc, KC vc,
                  float* part_o, float* part_ml, bf16_t* o, int B, int nh, int nkv, int S_max, int64_t ld, float scale2,
                  int window, Block blk, hipStream_t st, CA... ca) {
   const int rep = nh / nkv, nchunks = (S_max + SPLIT - 1) / SPLIT;
   const int row_tiles = (blk.Lb * rep + 32 * XW - 1) / (32 * XW);
-  hipLaunchKernelGGL((attn_extend_kernel<HD, CA...>), dim3((unsigned)(nkv * row_tiles), (unsigned)B, (unsigned)nchunks),
+  hipLaunchKernelGGL((attn_extend_kernel<HD, KC, CA...>), dim3((unsigned)(nkv * row_tiles), (unsigned)B, (unsigned)nchunks),
                      dim3(64 * XW), 0, st, qkv, pos, kstart, kc, vc, part_o, part_ml, nkv, rep, row_tiles, S_max, ld,
                      scale2, window, blk, ca...);
   hipLaunchKernelGGL(attn_extend_combine, dim3((unsigned)(blk.Lb * nh), (unsigned)B), dim3((unsigned)HD), 0, st, part_o,
@@ -315,8 +334,8 @@ int launch_block(const bf16_t* qkv, const int* pos, const int* kstart, const bf1
   return (int)hipGetLastError();
 }
 
-template <class... CA>
-int extend_blocks(const bf16_t* qkv, const int* pos, const int* kstart, const bf16_t* kc, const bf16_t* vc,
+template <class KC, class... CA>
+int extend_blocks(const bf16_t* qkv, const int* pos, const int* kstart, KC kc, KC vc,
                   float* part_o, float* part_ml, bf16_t* o, int B, int L, int nh, int nkv, int hd, int S_max,
                   int64_t ld, float scale2, int window, hipStream_t st, CA... ca) {
   for (int off = 0; off < L; off += QBLOCK) {
@@ -332,6 +351,7 @@ int extend_blocks(const bf16_t* qkv, const int* pos, const int* kstart, const bf
 
 }  // namespace
 
+#ifndef ND_EXTEND_KERNELS_ONLY  // attn_kv8.hip includes this file for everything but the library entries
 // Queries per attention launch: the workspace holds the partials of this many (tests aim at its edge).
 ND_API int nd_attn_extend_qblock() { return QBLOCK; }
 
@@ -357,6 +377,8 @@ ND_API int nd_attn_extend(void* qkv, const float* cosT, const float* sinT, const
   bf16_t* x = reinterpret_cast<bf16_t*>(qkv);
   bf16_t* kc = reinterpret_cast<bf16_t*>(kcache);
   bf16_t* vc = reinterpret_cast<bf16_t*>(vcache);
+  const bf16_t* kr = kc;  // the attention's read-only view: extend_blocks deduces its operand type from these
+  const bf16_t* vr = vc;
   const int64_t items = (int64_t)B * L * (nh + 2 * nkv) * (hd / 16);
   if ((items + 255) / 256 > 0x7fffffff) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(attn_extend_append, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, x, cosT, sinT, pos,
@@ -365,8 +387,9 @@ ND_API int nd_attn_extend(void* qkv, const float* cosT, const float* sinT, const
   if (err) return err;
   bf16_t* out = reinterpret_cast<bf16_t*>(o);
   if (cap != 0.f)
-    return extend_blocks(x, pos, kstart, kc, vc, part_o, part_ml, out, B, L, nh, nkv, hd, S_max, ld, scale, window, st,
+    return extend_blocks(x, pos, kstart, kr, vr, part_o, part_ml, out, B, L, nh, nkv, hd, S_max, ld, scale, window, st,
                          cap_args(cap));
-  return extend_blocks(x, pos, kstart, kc, vc, part_o, part_ml, out, B, L, nh, nkv, hd, S_max, ld, scale * LOG2E,
+  return extend_blocks(x, pos, kstart, kr, vr, part_o, part_ml, out, B, L, nh, nkv, hd, S_max, ld, scale * LOG2E,
                        window, st);
 }
+#endif  // ND_EXTEND_KERNELS_ONLY

@@ -71,12 +71,15 @@ FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"],
               # the capped attention kernels: the templates of attention.hip / attn_decode.hip in objects of their own
               "attn_softcap.hip": ["-fno-slp-vectorize"] + _NO_PK_F32,
               "attn_decode_cap.hip": _NO_PK_F32,
+              # the fp8 KV-cache kernels: attn_extend.hip's MFMA kernel on another staging path, with its flag
+              "attn_kv8.hip": ["-fno-slp-vectorize"],
               # gemm_w128.hip: its phases are 64-slot loops that must unroll completely (every
               # accumulator index a constant); past the default pragma threshold the accumulator array
               # silently moves to scratch
               "gemm_w128.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
 # Sources that include another source (for its kernel templates): rebuilt when that one changes, like a header.
-SOURCE_DEPS = {"attn_softcap.hip": ["attention.hip"], "attn_decode_cap.hip": ["attn_decode.hip"]}
+SOURCE_DEPS = {"attn_softcap.hip": ["attention.hip"], "attn_decode_cap.hip": ["attn_decode.hip"],
+               "attn_kv8.hip": ["attn_decode.hip", "attn_extend.hip"]}
 
 
 def _deps(src, headers):

@@ -3,7 +3,7 @@
     python -m nanodiloco_amd.generate --checkpoint DIR (--prompt-ids "1,2,3" ... | --prompt-file F | --prompt "text" ...)
         [--llama-config-file F] [--max-new-tokens 32] [--temperature 0] [--top-k 0] [--top-p 1.0] [--seed 0]
         [--dtype auto] [--residual-dtype auto] [--device auto] [--hip-graph auto|on|off]
-        [--tokenizer PATH] [--prefill-chunk 0]
+        [--tokenizer PATH] [--prefill-chunk 0] [--kv-dtype bf16|fp8]
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``), the config comes from ``--llama-config-file`` or the checkpoint's ``config.json`` -- as
@@ -14,7 +14,9 @@ of ids per line.  The prompts form one left-padded batch.  Output: one JSON line
 ``prefill_s``, ``decode_s`` and ``decode_tokens_per_s``.  ``--tokenizer PATH`` (optional) encodes ``--prompt`` and decodes
 the result through ``AutoTokenizer.from_pretrained(PATH, local_files_only=True)``: nothing is ever fetched; without
 it only ids are accepted.  ``--prefill-chunk N`` (N > 0) prefills the prompt in pieces of N tokens through the
-multi-token KV-cache attention (``model.extend``) instead of one whole-prompt forward.
+multi-token KV-cache attention (``model.extend``) instead of one whole-prompt forward.  ``--kv-dtype fp8`` keeps the KV
+cache as e4m3 codes plus one exponent per row (about half the bytes of bf16; docs/DESIGN.md "fp8 KV cache"); the
+timing line then echoes the value as ``kv_dtype``.
 """
 from __future__ import annotations
 
@@ -47,6 +49,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hip-graph", default="auto", choices=["auto", "on", "off"])
     p.add_argument("--prefill-chunk", type=int, default=0,
                    help="prefill the prompt in pieces of N tokens through model.extend (0: one whole-prompt forward)")
+    p.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+                   help="KV cache storage: bf16, or fp8 (e4m3 codes + one exponent per row)")
     return p
 
 
@@ -102,7 +106,8 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
         mask[i, T - len(p):] = 1
     ids, mask = ids.to(device), mask.to(device)
     kw = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed,
-              hip_graph={"auto": "auto", "on": True, "off": False}[a.hip_graph], prefill_chunk=a.prefill_chunk)
+              hip_graph={"auto": "auto", "on": True, "off": False}[a.hip_graph], prefill_chunk=a.prefill_chunk,
+              kv_dtype=a.kv_dtype)
     amask = mask if len(prompts) > 1 else None
 
     def sync():
@@ -136,6 +141,8 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
     decode_s = max(total_s - prefill_s, 0.0)
     timing = {"prefill_s": prefill_s, "decode_s": decode_s,
               "decode_tokens_per_s": (steps * len(prompts) / decode_s) if decode_s > 0 and steps else 0.0}
+    if a.kv_dtype != "bf16":  # the default run's line is unchanged
+        timing["kv_dtype"] = a.kv_dtype
     print(json.dumps(timing), flush=True)
     return recs + [timing]
 

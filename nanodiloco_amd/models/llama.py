@@ -305,8 +305,9 @@ class LlamaForCausalLM:
         finally:
             self.training, self.proj = saved
 
-    def new_cache(self, batch: int, s_max: int):
-        return ops.KVCache(self.config, batch, s_max, self.device, self.compute_dtype)
+    def new_cache(self, batch: int, s_max: int, kv_dtype: str = "bf16"):
+        """``kv_dtype`` "fp8": K and V rows as e4m3 codes plus a row exponent (``ops.decode``), about half the bytes."""
+        return ops.KVCache(self.config, batch, s_max, self.device, self.compute_dtype, kv_dtype=kv_dtype)
 
     def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], cache,
                 chunk: int = 0) -> torch.Tensor:
@@ -414,7 +415,8 @@ class LlamaForCausalLM:
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                  max_new_tokens: int = 32, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  eos_token_id=_CONFIG, pad_token_id=_CONFIG, seed: int = 0, use_cache: bool = True,
-                 hip_graph="auto", return_logits: bool = False, prefill_chunk: int = 0):
+                 hip_graph="auto", return_logits: bool = False, prefill_chunk: int = 0,
+                 kv_dtype: str = "bf16"):
         """Continue a (left-padded) prompt batch ``input_ids`` [B, T]; returns the token ids [B, T + n], n <=
         ``max_new_tokens`` (generation ends early once every row has produced ``eos_token_id``; a finished row is
         filled with ``pad_token_id``).  ``temperature`` 0 is greedy; otherwise ``filter_logits`` (top-k, top-p) and
@@ -422,8 +424,11 @@ class LlamaForCausalLM:
         per token (the check and the timing baseline).  ``hip_graph``: True / False / "auto" (on for a GPU, non-fp8
         model on the HIP path): the decode step is captured once after two eager steps and replayed.
         ``return_logits``: also the fp32 logits [B, n, V] every token was drawn from.  ``prefill_chunk`` = N > 0 (with
-        ``use_cache``): the prompt is prefilled through ``extend`` in pieces of N tokens."""
+        ``use_cache``): the prompt is prefilled through ``extend`` in pieces of N tokens.  ``kv_dtype``: "bf16", or "fp8"
+        for the 8-bit KV cache (``new_cache``; needs ``use_cache``)."""
         c = self.config
+        if kv_dtype != "bf16" and not use_cache:
+            raise ValueError("kv_dtype needs use_cache=True")
         eos = c.eos_token_id if eos_token_id is _CONFIG else eos_token_id
         pad = pad_token_id
         if pad is _CONFIG or pad is None:
@@ -448,7 +453,7 @@ class LlamaForCausalLM:
         if hip_graph and (not use_cache or dev.type != "cuda"):
             raise ValueError("hip_graph needs use_cache=True on a GPU")
         if use_cache:
-            cache = self.new_cache(B, T + n - 1)  # the last token drawn is never fed back
+            cache = self.new_cache(B, T + n - 1, kv_dtype=kv_dtype)  # the last token drawn is never fed back
             logits = self.prefill(input_ids, attention_mask, cache, chunk=int(prefill_chunk))
             step = functools.partial(self.decode_step, cache=cache)
             if hip_graph:

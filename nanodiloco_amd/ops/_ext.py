@@ -172,6 +172,13 @@ def _declare(L: ctypes.CDLL):
         # ..., o, B, L, nh, nkv, hd, S_max, ld, scale, window (0 = none), cap (0 = none), stream
         "nd_attn_extend": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L64, F, I, F, P],
         "nd_attn_extend_qblock": [],
+        # the same two steps and the prefill fill on an fp8 (e4m3 + row exponent) cache (csrc/attn_kv8.hip)
+        # qkv, cos, sin, pos, kstart, kcodes, kexp, vcodes, vexp, part_o, part_ml, o, B, [L,] nh, nkv, hd, S_max, ld,
+        # scale, window (0 = none), stream
+        "nd_attn_decode_kv8": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L64, F, I, P],
+        "nd_attn_extend_kv8": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L64, F, I, P],
+        # qkv, kcodes, kexp, vcodes, vexp, B, T, nh, nkv, hd, S_max, ld, stream
+        "nd_kv8_fill": [P, P, P, P, P, I, I, I, I, I, I, L64, P],
         # mlp
         "nd_swiglu_fwd": [P, P, I, L64, I, P],
         "nd_swiglu_bwd": [P, P, P, I, L64, I, P],

@@ -26,6 +26,13 @@ not advanced: ``cache.advance(L)``.
 
 ``cache_fill`` is the prefill side: it copies the k|v columns of the training path's packed q|k|v buffer into slots
 ``0 .. T-1``.
+
+``KVCache(..., kv_dtype="fp8")`` stores every K row (after RoPE) and V row as ``hd`` e4m3 codes plus one int8 exponent
+(``kv8_quantize`` / ``kv8_dequantize`` below are the format's definition; docs/DESIGN.md "fp8 KV cache"): ``k`` / ``v``
+are uint8 ``[B, nkv, S_max, hd]`` and ``k_exp`` / ``v_exp`` int8 ``[B, nkv, S_max]``.  The three entry points dispatch on
+the cache; the HIP path is ``csrc/attn_kv8.hip`` (``nd_attn_decode_kv8``, ``nd_attn_extend_kv8``, ``nd_kv8_fill``), the
+PyTorch twin dequantises the cache, runs the bf16 twins with the new rows passed through the quantiser, and stores the
+new rows' codes.  The fp8 kernels do not carry attention soft-capping: such a config is refused at construction.
 """
 from __future__ import annotations
 
@@ -66,9 +73,37 @@ def extend_workspace(B: int, nh: int, hd: int, s_max: int, device):
             torch.empty(n, 2, dtype=torch.float32, device=device))
 
 
+KV_DTYPES = ("bf16", "fp8")
+KV8_EXP_MIN, KV8_EXP_MAX = -100, 100
+
+
+def kv8_quantize(rows: torch.Tensor):
+    """The fp8 cache format: ``rows`` [..., hd] (any float dtype, taken as fp32) -> (codes uint8 [..., hd], exps int8
+    [...]), value = code * 2^e.  Per row, amax = max |x| = f 2^k with f in [0.5, 1): e = k - 9 if f <= 0.875 else k - 8
+    (the smallest e with amax 2^-e <= 448), clamped to [-100, 100]; e = 0 for a zero row.  code = e4m3(x 2^-e),
+    round-to-nearest-even, saturating; the scaling is by a power of two, so the code is a pure function of the row.
+    Outside the contract (as the kernels): a row with an infinity gets e = 100; a NaN stays out of the amax and
+    becomes the NaN code."""
+    x = rows.float()
+    amax = x.abs().nan_to_num(nan=0.0).amax(-1)
+    f, k = torch.frexp(amax)
+    e = torch.where(f <= 0.875, k - 9, k - 8)
+    e = torch.where(torch.isinf(amax), torch.full_like(e, KV8_EXP_MAX), e).clamp(KV8_EXP_MIN, KV8_EXP_MAX)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    scaled = torch.ldexp(x, -e[..., None]).clamp(-448.0, 448.0)  # the cast alone would turn > 448 into NaN
+    return scaled.to(torch.float8_e4m3fn).view(torch.uint8), e.to(torch.int8)
+
+
+def kv8_dequantize(codes: torch.Tensor, exps: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """code * 2^e: exact in fp32 and in bf16 (4 significant bits, never below the smallest normal)."""
+    return torch.ldexp(codes.view(torch.float8_e4m3fn).float(), exps.int()[..., None]).to(dtype)
+
+
 class KVCache:
-    def __init__(self, config, batch: int, s_max: int, device, dtype: torch.dtype):
+    def __init__(self, config, batch: int, s_max: int, device, dtype: torch.dtype, kv_dtype: str = "bf16"):
         c = config
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"KVCache: kv_dtype must be one of {KV_DTYPES}, not {kv_dtype!r}")
         if batch < 1 or s_max < 1:
             raise ValueError("KVCache needs batch >= 1 and s_max >= 1")
         if s_max > c.max_position_embeddings:
@@ -84,9 +119,21 @@ class KVCache:
         self.window = int(getattr(c, "sliding_window", None) or 0) or None
         # attention soft-cap (None = off): the decode scores are capped as the training kernels cap theirs
         self.softcap = ref.check_attn_softcap(getattr(c, "attn_logit_softcapping", None))
+        self.kv_dtype = kv_dtype
         shape = (self.batch, self.nkv, self.s_max, self.hd)
-        self.k = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(c.num_hidden_layers)]
-        self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(c.num_hidden_layers)]
+        layers = range(c.num_hidden_layers)
+        if kv_dtype == "fp8":
+            if self.softcap is not None:
+                raise ValueError("KVCache: kv_dtype='fp8' does not support attn_logit_softcapping (the fp8 cache "
+                                 "kernels carry no soft-cap); use kv_dtype='bf16'")
+            self.k = [torch.zeros(shape, dtype=torch.uint8, device=self.device) for _ in layers]
+            self.v = [torch.zeros(shape, dtype=torch.uint8, device=self.device) for _ in layers]
+            self.k_exp = [torch.zeros(shape[:3], dtype=torch.int8, device=self.device) for _ in layers]
+            self.v_exp = [torch.zeros(shape[:3], dtype=torch.int8, device=self.device) for _ in layers]
+        else:
+            self.k = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in layers]
+            self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in layers]
+            self.k_exp = self.v_exp = None
         self.pos = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
         self.kstart = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
         # host-side upper bound of pos: lets every step refuse a full cache without reading the device
@@ -216,9 +263,118 @@ def attn_decode_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_
     return out
 
 
+def _check_kv8_launch(tag, qkv, cos, sin, pos, kstart, kcodes, kexp, vcodes, vexp, part_o, part_ml, L, nh, nkv, hd, out):
+    """Everything ``nd_attn_decode_kv8`` (``L`` None) / ``nd_attn_extend_kv8`` rely on; returns (B, s_max, out)."""
+    if hd not in HEAD_DIMS:
+        raise ValueError(f"{tag}: head_dim {hd} not in {HEAD_DIMS}")
+    if nh < 1 or nkv < 1 or nh % nkv or nh // nkv > MAX_REP:
+        raise ValueError(f"{tag}: nh = {nh}, nkv = {nkv}: need nh % nkv == 0 and nh / nkv <= {MAX_REP}")
+    for name, t, dt in (("kcache", kcodes, torch.uint8), ("vcache", vcodes, torch.uint8), ("k_exp", kexp, torch.int8),
+                        ("v_exp", vexp, torch.int8)):
+        if t.dtype != dt or not t.is_cuda:
+            raise ValueError(f"{tag}: {name} must be a {str(dt)[6:]} GPU tensor")
+    if kcodes.dim() != 4 or kcodes.shape != vcodes.shape or kcodes.shape[1] != nkv or kcodes.shape[3] != hd:
+        raise ValueError(f"{tag}: the code caches must be [B, nkv, S_max, hd]")
+    B, _, s_max, _ = kcodes.shape
+    if B < 1 or s_max < 1:
+        raise ValueError(f"{tag}: empty cache")
+    if tuple(kexp.shape) != (B, nkv, s_max) or tuple(vexp.shape) != (B, nkv, s_max):
+        raise ValueError(f"{tag}: the exponents must be [B, nkv, S_max] = [{B}, {nkv}, {s_max}]")
+    for name, t in (("kcache", kcodes), ("vcache", vcodes), ("k_exp", kexp), ("v_exp", vexp)):
+        if not t.is_contiguous():
+            raise ValueError(f"{tag}: {name} must be contiguous")
+    n = 1 if L is None else L
+    if n < 1 or n > s_max:
+        raise ValueError(f"{tag}: L = {n} new tokens outside [1, s_max = {s_max}]")
+    W = (nh + 2 * nkv) * hd
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B * n, W):
+        raise ValueError(f"{tag}: qkv must be [{B * n}, {W}]")
+    if qkv.dtype != torch.bfloat16 or not qkv.is_cuda:
+        raise ValueError(f"{tag}: qkv must be a bf16 GPU tensor")
+    if qkv.stride(1) != 1 or qkv.stride(0) < W or qkv.stride(0) % 8:
+        raise ValueError(f"{tag}: qkv rows must be contiguous with a stride that is a multiple of 8")
+    for name, t in (("cos", cos), ("sin", sin)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != hd \
+                or t.shape[0] < s_max:
+            raise ValueError(f"{tag}: {name} must be a contiguous fp32 [>= {s_max}, {hd}] GPU table")
+    for name, t in (("pos", pos), ("kstart", kstart)):
+        if t is None and name == "kstart":
+            continue
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() != B:
+            raise ValueError(f"{tag}: {name} must be a contiguous int32 [{B}] GPU tensor")
+    need = B * nh * ((s_max + decode_split() - 1) // decode_split()) * (1 if L is None else min(L, extend_qblock()))
+    for name, t, cols in (("part_o", part_o, hd), ("part_ml", part_ml, 2)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < need * cols:
+            raise ValueError(f"{tag}: {name} must be a contiguous fp32 workspace of {need * cols}")
+    if out is None:
+        out = torch.empty(B * n, nh * hd, dtype=torch.bfloat16, device=qkv.device)
+    elif out.dtype != torch.bfloat16 or not out.is_cuda or not out.is_contiguous() \
+            or tuple(out.shape) != (B * n, nh * hd):
+        raise ValueError(f"{tag}: out must be a contiguous bf16 [{B * n}, {nh * hd}] GPU tensor")
+    for name, t in (("qkv", qkv), ("cos", cos), ("sin", sin), ("kcache", kcodes), ("vcache", vcodes),
+                    ("part_o", part_o), ("part_ml", part_ml)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{tag}: {name} must be 16-byte aligned")
+    return B, s_max, out
+
+
+def attn_decode_kv8_launch(qkv, cos, sin, pos, kstart, kcodes, kexp, vcodes, vexp, part_o, part_ml, nh: int, nkv: int,
+                           hd: int, out: Optional[torch.Tensor] = None, window: Optional[int] = None) -> torch.Tensor:
+    """``nd_attn_decode_kv8`` on raw tensors: ``attn_decode_launch`` on an fp8 cache (codes uint8 [B, nkv, S_max, hd],
+    exponents int8 [B, nkv, S_max]); every shape, dtype, contiguity and alignment is checked before the launch."""
+    window = _check_window(window)
+    B, s_max, out = _check_kv8_launch("fp8 decode attention", qkv, cos, sin, pos, kstart, kcodes, kexp, vcodes, vexp,
+                                      part_o, part_ml, None, nh, nkv, hd, out)
+    _ext.check(_ext.lib().nd_attn_decode_kv8(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos),
+                                             _ext.ptr(kstart), _ext.ptr(kcodes), _ext.ptr(kexp), _ext.ptr(vcodes),
+                                             _ext.ptr(vexp), _ext.ptr(part_o), _ext.ptr(part_ml), _ext.ptr(out), B, nh,
+                                             nkv, hd, s_max, qkv.stride(0), float(hd ** -0.5),
+                                             min(window or 0, 2 ** 31 - 1), _ext.stream_ptr(qkv.device)),
+               "nd_attn_decode_kv8")
+    return out
+
+
+def attn_extend_kv8_launch(qkv, cos, sin, pos, kstart, kcodes, kexp, vcodes, vexp, part_o, part_ml, L: int, nh: int,
+                           nkv: int, hd: int, out: Optional[torch.Tensor] = None,
+                           window: Optional[int] = None) -> torch.Tensor:
+    """``nd_attn_extend_kv8`` on raw tensors: ``attn_extend_launch`` on an fp8 cache (``qkv`` is overwritten: q and k
+    rotated in place); checked like ``attn_decode_kv8_launch``."""
+    window = _check_window(window)
+    B, s_max, out = _check_kv8_launch("fp8 extend attention", qkv, cos, sin, pos, kstart, kcodes, kexp, vcodes, vexp,
+                                      part_o, part_ml, int(L), nh, nkv, hd, out)
+    _ext.check(_ext.lib().nd_attn_extend_kv8(_ext.ptr(qkv), _ext.ptr(cos), _ext.ptr(sin), _ext.ptr(pos),
+                                             _ext.ptr(kstart), _ext.ptr(kcodes), _ext.ptr(kexp), _ext.ptr(vcodes),
+                                             _ext.ptr(vexp), _ext.ptr(part_o), _ext.ptr(part_ml), _ext.ptr(out), B,
+                                             int(L), nh, nkv, hd, s_max, qkv.stride(0), float(hd ** -0.5),
+                                             min(window or 0, 2 ** 31 - 1), _ext.stream_ptr(qkv.device)),
+               "nd_attn_extend_kv8")
+    return out
+
+
+def _kv8_twin(fn, cache, layer: int, slots: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
+    """An fp8 cache through a bf16 twin ``fn(kcache, vcache, kv_round)``: the layer is dequantised, the new rows pass through the quantiser on
+    their way into it (``kv_round``: they enter this step's attention as every later step sees them), and their codes
+    and exponents are stored in ``slots`` ([B] or [B, L])."""
+    kd = kv8_dequantize(cache.k[layer], cache.k_exp[layer], dt)
+    vd = kv8_dequantize(cache.v[layer], cache.v_exp[layer], dt)
+    new = {}
+
+    def kv_round(k, v):  # k, v: the new rows as the twin indexes them into the cache, [B, (L,) nkv, hd]
+        new["k"], new["v"] = kv8_quantize(k), kv8_quantize(v)
+        return kv8_dequantize(*new["k"], dt), kv8_dequantize(*new["v"], dt)
+
+    o = fn(kd, vd, kv_round)
+    rows = torch.arange(cache.batch, device=slots.device).view(-1, *([1] * (slots.dim() - 1)))
+    for codes, exps, (c, e) in ((cache.k[layer], cache.k_exp[layer], new["k"]), (cache.v[layer], cache.v_exp[layer], new["v"])):
+        codes[rows, :, slots] = c
+        exps[rows, :, slots] = e
+    return o
+
+
 def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, nkv: int, hd: int,
-                           window: Optional[int] = None, softcap: Optional[float] = None) -> torch.Tensor:
-    """The PyTorch twin on raw tensors (any device / float dtype); same contract as ``attn_decode_launch``."""
+                           window: Optional[int] = None, softcap: Optional[float] = None, kv_round=None) -> torch.Tensor:
+    """The PyTorch twin on raw tensors (any device / float dtype); same contract as ``attn_decode_launch``.
+    ``kv_round`` (the fp8 cache's twin): maps the new (k, v) rows to what is stored and attended."""
     window = _check_window(window)
     softcap = ref.check_attn_softcap(softcap)
     B, _, s_max, _ = kcache.shape
@@ -228,8 +384,11 @@ def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, 
     q = ref.apply_rope(q.reshape(B, nh, 1, hd), c, s)
     k = ref.apply_rope(k.reshape(B, nkv, 1, hd), c, s)
     rows = torch.arange(B, device=qkv.device)
-    kcache[rows, :, p] = k[:, :, 0]
-    vcache[rows, :, p] = v.reshape(B, nkv, hd)
+    knew, vnew = k[:, :, 0], v.reshape(B, nkv, hd)
+    if kv_round is not None:
+        knew, vnew = kv_round(knew, vnew)
+    kcache[rows, :, p] = knew
+    vcache[rows, :, p] = vnew
     t = torch.arange(s_max, device=qkv.device)
     lo = kstart.long().view(B, 1) if kstart is not None else torch.zeros(B, 1, dtype=torch.long, device=qkv.device)
     if window is not None:
@@ -252,12 +411,22 @@ def attention_decode_torch(qkv, cos, sin, pos, kstart, kcache, vcache, nh: int, 
 def attention_decode(qkv: torch.Tensor, cache: KVCache, layer: int, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     """One decode step of layer ``layer``; see the module doc.  Returns o [B, nh * hd]."""
     _check_cache_args(qkv, cos, sin, cache, layer)
+    fp8 = cache.kv_dtype == "fp8"
     if _ext.use_hip(qkv):
         if cache.part_o is None:
             cache.part_o, cache.part_ml = decode_workspace(cache.batch, cache.nh, cache.hd, cache.s_max, cache.device)
+        if fp8:
+            return attn_decode_kv8_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.k_exp[layer],
+                                          cache.v[layer], cache.v_exp[layer], cache.part_o, cache.part_ml, cache.nh,
+                                          cache.nkv, cache.hd, window=cache.window)
         return attn_decode_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.part_o,
                                   cache.part_ml, cache.nh, cache.nkv, cache.hd, window=cache.window,
                                   softcap=cache.softcap)
+    if fp8:
+        return _kv8_twin(lambda kd, vd, rnd: attention_decode_torch(qkv, cos, sin, cache.pos, cache.kstart, kd, vd,
+                                                                    cache.nh, cache.nkv, cache.hd, window=cache.window,
+                                                                    kv_round=rnd),
+                         cache, layer, cache.pos.long(), qkv.dtype)
     return attention_decode_torch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.nh,
                                   cache.nkv, cache.hd, window=cache.window, softcap=cache.softcap)
 
@@ -322,9 +491,10 @@ def attn_extend_launch(qkv, cos, sin, pos, kstart, kcache, vcache, part_o, part_
 
 
 def attention_extend_torch(qkv, cos, sin, pos, kstart, kcache, vcache, L: int, nh: int, nkv: int, hd: int,
-                           window: Optional[int] = None, softcap: Optional[float] = None) -> torch.Tensor:
+                           window: Optional[int] = None, softcap: Optional[float] = None, kv_round=None) -> torch.Tensor:
     """The PyTorch twin on raw tensors (any device / float dtype); same contract as ``attn_extend_launch`` except that
-    ``qkv`` is left alone: rotation at ``pos + i``, slot writes by index, a masked fp32 softmax over the whole cache."""
+    ``qkv`` is left alone: rotation at ``pos + i``, slot writes by index, a masked fp32 softmax over the whole cache.
+    ``kv_round``: as ``attention_decode_torch``."""
     window = _check_window(window)
     softcap = ref.check_attn_softcap(softcap)
     B, _, s_max, _ = kcache.shape
@@ -334,8 +504,11 @@ def attention_extend_torch(qkv, cos, sin, pos, kstart, kcache, vcache, L: int, n
     q = ref.apply_rope(q.reshape(B, L, nh, hd).transpose(1, 2), c, s)
     k = ref.apply_rope(k.reshape(B, L, nkv, hd).transpose(1, 2), c, s)
     rows = torch.arange(B, device=qkv.device).view(B, 1)
-    kcache[rows, :, slot] = k.transpose(1, 2).to(kcache.dtype)  # indexed [B, L, nkv, hd]
-    vcache[rows, :, slot] = v.reshape(B, L, nkv, hd).to(vcache.dtype)
+    knew, vnew = k.transpose(1, 2), v.reshape(B, L, nkv, hd)
+    if kv_round is not None:
+        knew, vnew = kv_round(knew, vnew)
+    kcache[rows, :, slot] = knew.to(kcache.dtype)  # indexed [B, L, nkv, hd]
+    vcache[rows, :, slot] = vnew.to(vcache.dtype)
     t = torch.arange(s_max, device=qkv.device)
     lo = kstart.long().view(B, 1) if kstart is not None else torch.zeros(B, 1, dtype=torch.long, device=qkv.device)
     lo = lo.expand(B, L)
@@ -367,14 +540,53 @@ def attention_extend(qkv: torch.Tensor, cache: KVCache, layer: int, cos: torch.T
     if cos.shape[0] < cache.s_max or cos.shape[1] != cache.hd or cos.shape != sin.shape:
         raise ValueError(f"the RoPE tables must be [>= s_max = {cache.s_max}, hd = {cache.hd}]")
     cache.check_room(L)
+    fp8 = cache.kv_dtype == "fp8"
     if _ext.use_hip(qkv):
         if cache.ext_o is None:
             cache.ext_o, cache.ext_ml = extend_workspace(cache.batch, cache.nh, cache.hd, cache.s_max, cache.device)
+        if fp8:
+            return attn_extend_kv8_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.k_exp[layer],
+                                          cache.v[layer], cache.v_exp[layer], cache.ext_o, cache.ext_ml, L, cache.nh,
+                                          cache.nkv, cache.hd, window=cache.window)
         return attn_extend_launch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], cache.ext_o,
                                   cache.ext_ml, L, cache.nh, cache.nkv, cache.hd, window=cache.window,
                                   softcap=cache.softcap)
+    if fp8:
+        slots = cache.pos.long().view(-1, 1) + torch.arange(L, device=qkv.device)
+        return _kv8_twin(lambda kd, vd, rnd: attention_extend_torch(qkv, cos, sin, cache.pos, cache.kstart, kd, vd, L,
+                                                                    cache.nh, cache.nkv, cache.hd, window=cache.window,
+                                                                    kv_round=rnd),
+                         cache, layer, slots, qkv.dtype)
     return attention_extend_torch(qkv, cos, sin, cache.pos, cache.kstart, cache.k[layer], cache.v[layer], L, cache.nh,
                                   cache.nkv, cache.hd, window=cache.window, softcap=cache.softcap)
+
+
+def kv8_fill_launch(qkv, kcodes, kexp, vcodes, vexp, T: int, nh: int, nkv: int, hd: int) -> None:
+    """``nd_kv8_fill`` on raw tensors: the k|v columns of the packed, rotated bf16 ``qkv`` [B*T, (nh + 2 nkv) hd]
+    quantised into slots ``0 .. T-1``; checked before the launch like the attention launchers."""
+    tag = "fp8 cache fill"
+    if hd not in HEAD_DIMS or nh < 1 or nkv < 1 or nh % nkv or nh // nkv > MAX_REP:
+        raise ValueError(f"{tag}: head_dim {hd} not in {HEAD_DIMS}, or nh = {nh}, nkv = {nkv} with nh / nkv > {MAX_REP}")
+    for name, t, dt in (("kcache", kcodes, torch.uint8), ("vcache", vcodes, torch.uint8), ("k_exp", kexp, torch.int8),
+                        ("v_exp", vexp, torch.int8)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{tag}: {name} must be a contiguous {str(dt)[6:]} GPU tensor")
+    if kcodes.dim() != 4 or kcodes.shape != vcodes.shape or kcodes.shape[1] != nkv or kcodes.shape[3] != hd:
+        raise ValueError(f"{tag}: the code caches must be [B, nkv, S_max, hd]")
+    B, _, s_max, _ = kcodes.shape
+    if tuple(kexp.shape) != (B, nkv, s_max) or tuple(vexp.shape) != (B, nkv, s_max):
+        raise ValueError(f"{tag}: the exponents must be [B, nkv, S_max] = [{B}, {nkv}, {s_max}]")
+    W = (nh + 2 * nkv) * hd
+    if T < 1 or T > s_max or qkv.dim() != 2 or tuple(qkv.shape) != (B * T, W):
+        raise ValueError(f"{tag}: qkv must be [B*T, {W}] with 1 <= T <= s_max = {s_max}, not {tuple(qkv.shape)}")
+    if qkv.dtype != torch.bfloat16 or not qkv.is_cuda or qkv.stride(1) != 1 or qkv.stride(0) < W or qkv.stride(0) % 8:
+        raise ValueError(f"{tag}: qkv must be a bf16 GPU tensor, rows contiguous with a stride that is a multiple of 8")
+    for name, t in (("qkv", qkv), ("kcache", kcodes), ("vcache", vcodes)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{tag}: {name} must be 16-byte aligned")
+    _ext.check(_ext.lib().nd_kv8_fill(_ext.ptr(qkv), _ext.ptr(kcodes), _ext.ptr(kexp), _ext.ptr(vcodes), _ext.ptr(vexp),
+                                      B, T, nh, nkv, hd, s_max, qkv.stride(0), _ext.stream_ptr(qkv.device)),
+               "nd_kv8_fill")
 
 
 def cache_fill(cache: KVCache, layer: int, qkv: torch.Tensor, B: int, T: int, cos=None, sin=None,
@@ -382,14 +594,26 @@ def cache_fill(cache: KVCache, layer: int, qkv: torch.Tensor, B: int, T: int, co
     """Prefill: the k|v columns of the packed q|k|v buffer [B*T, (nh + 2 nkv) hd] into slots ``0 .. T-1``.
     ``rotated=True``: the k columns already carry RoPE (the HIP training path rotates the buffer in place, or in the
     projection GEMM's epilogue).  ``rotated=False`` (the PyTorch path leaves its input alone): k is rotated here, with
-    the expression ``reference.attention_block`` uses.  A strided torch copy: not the hot path."""
+    the expression ``reference.attention_block`` uses.  A strided torch copy: not the hot path.  An fp8 cache
+    quantises the rows on the way: ``nd_kv8_fill`` on the HIP path, ``kv8_quantize`` otherwise."""
     nh, nkv, hd = cache.nh, cache.nkv, cache.hd
     if B != cache.batch or T > cache.s_max:
         raise ValueError(f"a [{B}, {T}] prompt does not fit a KV cache of batch {cache.batch}, s_max {cache.s_max}")
+    if cache.kv_dtype == "fp8" and _ext.use_hip(qkv):
+        if not rotated:
+            raise ValueError("cache_fill: the HIP fp8 fill takes an already rotated buffer")
+        kv8_fill_launch(qkv, cache.k[layer], cache.k_exp[layer], cache.v[layer], cache.v_exp[layer], T, nh, nkv, hd)
+        return
     x = qkv.view(B, T, (nh + 2 * nkv) * hd)
     k = x[..., nh * hd:(nh + nkv) * hd].reshape(B, T, nkv, hd).transpose(1, 2)
     v = x[..., (nh + nkv) * hd:].reshape(B, T, nkv, hd).transpose(1, 2)
     if not rotated:
         k = ref.apply_rope(k, cos[:T], sin[:T])
+    if cache.kv_dtype == "fp8":
+        for x, codes, exps in ((k, cache.k[layer], cache.k_exp[layer]), (v, cache.v[layer], cache.v_exp[layer])):
+            c, e = kv8_quantize(x)
+            codes[:, :, :T].copy_(c)
+            exps[:, :, :T].copy_(e)
+        return
     cache.k[layer][:, :, :T].copy_(k)
     cache.v[layer][:, :, :T].copy_(v)

@@ -13,7 +13,12 @@
            (``use_cache=False``, what the code could do before the cache) vs cached eager vs cached HIP graph, a host
            clock around the call with a device synchronise, rounds interleaved; tokens/s = B * new / seconds.
 
+  kv8    : ``--kv-dtype fp8``: ``nd_attn_decode_kv8`` against ``nd_attn_decode`` on the same numbers (B 32; 512 and 4096
+           keys; the 150M shape and nh 32 / nkv 8 / hd 128), alternating in one process, with the K/V bytes of a step
+           from shapes and the achieved bytes/s of both; then ``generate`` with both caches (profiles/kv8_decode.md).
+
     python scripts/decode_bench.py [--rounds 20] [--inner 20] [--e2e-rounds 3] [--skip-e2e] [--out FILE.md]
+                                   [--kv-dtype fp8]
 
 Needs a GPU: there is no CPU fall-back.
 """
@@ -111,6 +116,71 @@ def bench_window(name, B, length, window, rounds, inner, warmup, dev):
     return r
 
 
+KV8_SHAPES = {"150m": (16, 16, 64), "gqa128": (32, 8, 128)}
+
+
+def bench_kv8(name, B, length, rounds, inner, warmup, dev):
+    """``nd_attn_decode_kv8`` against ``nd_attn_decode`` at position ``length - 1``: the fp8 cache holds the quantised
+    rows, the bf16 cache their dequantised values (the same numbers), one timed burst of each per round."""
+    nh, nkv, hd = KV8_SHAPES[name]
+    g = torch.Generator(device=dev).manual_seed(B * 7 + length)
+    kq, ke = decode.kv8_quantize(torch.randn(B, nkv, length, hd, device=dev, generator=g).bfloat16())
+    vq, ve = decode.kv8_quantize(torch.randn(B, nkv, length, hd, device=dev, generator=g).bfloat16())
+    kc, vc = decode.kv8_dequantize(kq, ke, torch.bfloat16), decode.kv8_dequantize(vq, ve, torch.bfloat16)
+    qkv = torch.randn(B, (nh + 2 * nkv) * hd, device=dev, generator=g).bfloat16()
+    cos, sin = rope_cache(length, hd, 10000.0, None, dev)
+    pos = torch.full((B,), length - 1, dtype=torch.int32, device=dev)
+    ks = torch.zeros(B, dtype=torch.int32, device=dev)
+    part_o, part_ml = decode.decode_workspace(B, nh, hd, length, dev)
+    out = torch.empty(B, nh * hd, dtype=torch.bfloat16, device=dev)
+    fns = {"bf16": lambda: decode.attn_decode_launch(qkv, cos, sin, pos, ks, kc, vc, part_o, part_ml, nh, nkv, hd, out=out),
+           "fp8": lambda: decode.attn_decode_kv8_launch(qkv, cos, sin, pos, ks, kq, ke, vq, ve, part_o, part_ml, nh, nkv,
+                                                        hd, out=out)}
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ms, vals = {k: [] for k in fns}, {}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            t, o = timed(f, inner)
+            ms[k].append(t)
+            vals[k] = o.float().clone()
+    rows = 2 * B * nkv * length  # K and V rows a step reads
+    nbytes = {"bf16": rows * hd * 2, "fp8": rows * (hd + 1)}
+    r = {"shape": name, "B": B, "len": length, "rounds": rounds, "inner": inner,
+         "max_diff": float((vals["bf16"] - vals["fp8"]).abs().max()), "byte_ratio": (hd + 1) / (2 * hd)}
+    for k, v in ms.items():
+        r[k + "_us_median"], r[k + "_us_min"] = 1e3 * statistics.median(v), 1e3 * min(v)
+        r[k + "_MB"] = nbytes[k] / 1e6
+        r[k + "_GBps"] = nbytes[k] / (r[k + "_us_median"] * 1e-6) / 1e9
+    r["fp8_over_bf16"] = r["fp8_us_median"] / r["bf16_us_median"]
+    return r
+
+
+def bench_e2e_kv8(B, prompt, new, rounds, dev):
+    """``generate`` of Llama-150M with the HIP graph, bf16 cache against fp8 cache, rounds interleaved."""
+    from nanodiloco_amd.config import resolve_llama_config
+    from nanodiloco_amd.models import LlamaForCausalLM
+    m = LlamaForCausalLM(resolve_llama_config("llama_150m.json"), dev, torch.bfloat16).init_weights(0).eval()
+    ids = torch.randint(3, m.config.vocab_size, (B, prompt), device=dev)
+    secs = {"bf16": {1: [], new: []}, "fp8": {1: [], new: []}}
+    for timed_round in [False] + [True] * rounds:  # one untimed pass of every shape first
+        for kvd in secs:
+            for n in (1, new):  # the prompt pass alone, then the whole run: the difference is the decode time
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                m.generate(ids, max_new_tokens=n, eos_token_id=None, hip_graph=True, kv_dtype=kvd)
+                torch.cuda.synchronize()
+                if timed_round:
+                    secs[kvd][n].append(time.perf_counter() - t0)
+    r = {"B": B, "prompt": prompt, "new": new, "rounds": rounds}
+    for kvd, v in secs.items():
+        dec = statistics.median(v[new]) - statistics.median(v[1])
+        r[kvd + "_decode_s"], r[kvd + "_decode_tokens_per_s"] = dec, B * (new - 1) / dec
+    return r
+
+
 def bench_e2e(B, prompt, new, rounds, dev):
     from nanodiloco_amd.config import resolve_llama_config
     from nanodiloco_amd.models import LlamaForCausalLM
@@ -168,6 +238,9 @@ def main():
     ap.add_argument("--window", type=int, default=0,
                     help="time the sliding-window decode step (this many keys) against the full one at --len, and stop")
     ap.add_argument("--len", type=int, default=4096, help="with --window: keys in the cache (pos = len - 1)")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: time nd_attn_decode_kv8 against nd_attn_decode (B 32; 512 and 4096 keys) and generate "
+                         "with both caches, and stop")
     ap.add_argument("--out", default=None, help="also write the tables (markdown) here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -178,6 +251,13 @@ def main():
         for name in SHAPES:
             for B in (1, 8, 64):
                 print(json.dumps(bench_window(name, B, a.len, a.window, a.rounds, a.inner, a.warmup, dev)), flush=True)
+        return
+    if a.kv_dtype == "fp8":
+        for name in KV8_SHAPES:
+            for length in (512, 4096):
+                print(json.dumps(bench_kv8(name, 32, length, a.rounds, a.inner, a.warmup, dev)), flush=True)
+        if not a.skip_e2e:
+            print(json.dumps(bench_e2e_kv8(32, 512, 128, a.e2e_rounds, dev)), flush=True)
         return
     kern, e2e = [], []
     for name in SHAPES:
