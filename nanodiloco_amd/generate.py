@@ -3,7 +3,7 @@
     python -m nanodiloco_amd.generate --checkpoint DIR (--prompt-ids "1,2,3" ... | --prompt-file F | --prompt "text" ...)
         [--llama-config-file F] [--max-new-tokens 32] [--temperature 0] [--top-k 0] [--top-p 1.0] [--seed 0]
         [--dtype auto] [--residual-dtype auto] [--device auto] [--hip-graph auto|on|off]
-        [--tokenizer PATH] [--prefill-chunk 0] [--kv-dtype bf16|fp8]
+        [--tokenizer PATH] [--prefill-chunk 0] [--kv-dtype bf16|fp8] [--sampler torch|fused]
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``), the config comes from ``--llama-config-file`` or the checkpoint's ``config.json`` -- as
@@ -16,7 +16,9 @@ the result through ``AutoTokenizer.from_pretrained(PATH, local_files_only=True)`
 it only ids are accepted.  ``--prefill-chunk N`` (N > 0) prefills the prompt in pieces of N tokens through the
 multi-token KV-cache attention (``model.extend``) instead of one whole-prompt forward.  ``--kv-dtype fp8`` keeps the KV
 cache as e4m3 codes plus one exponent per row (about half the bytes of bf16; docs/DESIGN.md "fp8 KV cache"); the
-timing line then echoes the value as ``kv_dtype``.
+timing line then echoes the value as ``kv_dtype``.  ``--sampler fused`` (with ``--temperature`` > 0) draws every token
+with the one-launch HIP sampler (``ops.sample``; docs/DESIGN.md "Fused sampler") instead of ``filter_logits`` +
+``torch.multinomial``; the timing line then echoes ``sampler``.  The two draw different tokens from one seed.
 """
 from __future__ import annotations
 
@@ -51,6 +53,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="prefill the prompt in pieces of N tokens through model.extend (0: one whole-prompt forward)")
     p.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
                    help="KV cache storage: bf16, or fp8 (e4m3 codes + one exponent per row)")
+    p.add_argument("--sampler", default="torch", choices=["torch", "fused"],
+                   help="with --temperature > 0: torch (filter_logits + multinomial) or fused (ops.sample, one launch)")
     return p
 
 
@@ -107,7 +111,7 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
     ids, mask = ids.to(device), mask.to(device)
     kw = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed,
               hip_graph={"auto": "auto", "on": True, "off": False}[a.hip_graph], prefill_chunk=a.prefill_chunk,
-              kv_dtype=a.kv_dtype)
+              kv_dtype=a.kv_dtype, sampler=a.sampler)
     amask = mask if len(prompts) > 1 else None
 
     def sync():
@@ -143,6 +147,8 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
               "decode_tokens_per_s": (steps * len(prompts) / decode_s) if decode_s > 0 and steps else 0.0}
     if a.kv_dtype != "bf16":  # the default run's line is unchanged
         timing["kv_dtype"] = a.kv_dtype
+    if a.sampler != "torch":
+        timing["sampler"] = a.sampler
     print(json.dumps(timing), flush=True)
     return recs + [timing]
 

@@ -416,7 +416,7 @@ class LlamaForCausalLM:
                  max_new_tokens: int = 32, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  eos_token_id=_CONFIG, pad_token_id=_CONFIG, seed: int = 0, use_cache: bool = True,
                  hip_graph="auto", return_logits: bool = False, prefill_chunk: int = 0,
-                 kv_dtype: str = "bf16"):
+                 kv_dtype: str = "bf16", sampler: str = "torch"):
         """Continue a (left-padded) prompt batch ``input_ids`` [B, T]; returns the token ids [B, T + n], n <=
         ``max_new_tokens`` (generation ends early once every row has produced ``eos_token_id``; a finished row is
         filled with ``pad_token_id``).  ``temperature`` 0 is greedy; otherwise ``filter_logits`` (top-k, top-p) and
@@ -425,8 +425,12 @@ class LlamaForCausalLM:
         model on the HIP path): the decode step is captured once after two eager steps and replayed.
         ``return_logits``: also the fp32 logits [B, n, V] every token was drawn from.  ``prefill_chunk`` = N > 0 (with
         ``use_cache``): the prompt is prefilled through ``extend`` in pieces of N tokens.  ``kv_dtype``: "bf16", or "fp8"
-        for the 8-bit KV cache (``new_cache``; needs ``use_cache``)."""
+        for the 8-bit KV cache (``new_cache``; needs ``use_cache``).  ``sampler``: "torch" (``filter_logits`` +
+        ``torch.multinomial``) or "fused" (``ops.sample`` on one ``torch.rand`` number per row from the same seeded
+        generator: one HIP launch on the GPU); greedy is argmax under either."""
         c = self.config
+        if sampler not in ("torch", "fused"):
+            raise ValueError(f"sampler must be 'torch' or 'fused', not {sampler!r}")
         if kv_dtype != "bf16" and not use_cache:
             raise ValueError("kv_dtype needs use_cache=True")
         eos = c.eos_token_id if eos_token_id is _CONFIG else eos_token_id
@@ -473,7 +477,7 @@ class LlamaForCausalLM:
         for i in range(n):
             if kept is not None:
                 kept.append(logits.clone())  # a graphed step returns its static buffer
-            tok = sample_logits(logits, temperature, top_k, top_p, gen).to(input_ids.dtype)
+            tok = sample_logits(logits, temperature, top_k, top_p, gen, sampler=sampler).to(input_ids.dtype)
             if eos is not None:
                 tok = torch.where(finished, torch.full_like(tok, pad), tok)
                 finished = finished | (tok == eos)
@@ -520,9 +524,15 @@ def filter_logits(logits: torch.Tensor, top_k: int = 0, top_p: float = 1.0) -> t
 
 
 def sample_logits(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                  generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """One token id per row of fp32 ``logits`` [B, V]: argmax at temperature 0, else a seeded multinomial draw."""
+                  generator: Optional[torch.Generator] = None, sampler: str = "torch") -> torch.Tensor:
+    """One token id per row of fp32 ``logits`` [B, V]: argmax at temperature 0, else a seeded draw -- ``sampler``
+    "torch": ``filter_logits`` and a multinomial draw; "fused": ``ops.sample`` on one uniform number per row."""
+    if sampler not in ("torch", "fused"):
+        raise ValueError(f"sampler must be 'torch' or 'fused', not {sampler!r}")
     if temperature == 0:
         return logits.argmax(-1)
+    if sampler == "fused":
+        u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
+        return ops.sample(logits.float(), u, temperature, top_k, top_p)
     x = filter_logits(logits.float() / temperature, top_k, top_p)
     return torch.multinomial(torch.softmax(x, dim=-1), 1, generator=generator)[:, 0]

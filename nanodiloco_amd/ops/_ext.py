@@ -179,6 +179,8 @@ def _declare(L: ctypes.CDLL):
         "nd_attn_extend_kv8": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L64, F, I, P],
         # qkv, kcodes, kexp, vcodes, vexp, B, T, nh, nkv, hd, S_max, ld, stream
         "nd_kv8_fill": [P, P, P, P, P, I, I, I, I, I, I, L64, P],
+        # fused sampler (csrc/sample.hip): logits, u, tok, thr, nkept, B, V, ld, temperature, top_k, top_p, stream
+        "nd_sample_topk_topp": [P, P, P, P, P, I, I, L64, F, I, F, P],
         # mlp
         "nd_swiglu_fwd": [P, P, I, L64, I, P],
         "nd_swiglu_bwd": [P, P, P, I, L64, I, P],
