@@ -4,6 +4,7 @@
         [--llama-config-file F] [--max-new-tokens 32] [--temperature 0] [--top-k 0] [--top-p 1.0] [--seed 0]
         [--dtype auto] [--residual-dtype auto] [--device auto] [--hip-graph auto|on|off]
         [--tokenizer PATH] [--prefill-chunk 0] [--kv-dtype bf16|fp8] [--sampler torch|fused]
+        [--weight-dtype bf16|fp8]
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``), the config comes from ``--llama-config-file`` or the checkpoint's ``config.json`` -- as
@@ -18,11 +19,15 @@ multi-token KV-cache attention (``model.extend``) instead of one whole-prompt fo
 cache as e4m3 codes plus one exponent per row (about half the bytes of bf16; docs/DESIGN.md "fp8 KV cache"); the
 timing line then echoes the value as ``kv_dtype``.  ``--sampler fused`` (with ``--temperature`` > 0) draws every token
 with the one-launch HIP sampler (``ops.sample``; docs/DESIGN.md "Fused sampler") instead of ``filter_logits`` +
-``torch.multinomial``; the timing line then echoes ``sampler``.  The two draw different tokens from one seed.
+``torch.multinomial``; the timing line then echoes ``sampler``.  The two draw different tokens from one seed.  ``--weight-dtype fp8`` runs the decoder's projections and the
+lm head on e4m3 codes plus one exponent per 128 input features (``model.quantized_weights``; docs/DESIGN.md "fp8
+weight-only decode"): the decode step streams the codes through ``ops.gemv_w8``, every other path computes with the
+same rounded weights; the timing line then echoes ``weight_dtype``.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -55,6 +60,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="KV cache storage: bf16, or fp8 (e4m3 codes + one exponent per row)")
     p.add_argument("--sampler", default="torch", choices=["torch", "fused"],
                    help="with --temperature > 0: torch (filter_logits + multinomial) or fused (ops.sample, one launch)")
+    p.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
+                   help="projection weights: bf16, or fp8 weight-only (e4m3 codes + one exponent per 128 inputs)")
     return p
 
 
@@ -111,7 +118,7 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
     ids, mask = ids.to(device), mask.to(device)
     kw = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed,
               hip_graph={"auto": "auto", "on": True, "off": False}[a.hip_graph], prefill_chunk=a.prefill_chunk,
-              kv_dtype=a.kv_dtype, sampler=a.sampler)
+              kv_dtype=a.kv_dtype, sampler=a.sampler, weight_dtype=a.weight_dtype)
     amask = mask if len(prompts) > 1 else None
 
     def sync():
@@ -120,16 +127,18 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
 
     # the prompt pass alone (one new token), then the whole run: their difference is the decode time; one untimed
     # pass first, so that neither carries the first launches (code objects, GEMM algorithm selection)
-    model.generate(ids, amask, max_new_tokens=1, **kw)
-    sync()
-    t0 = time.perf_counter()
-    model.generate(ids, amask, max_new_tokens=1, **kw)
-    sync()
-    prefill_s = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    out = model.generate(ids, amask, max_new_tokens=a.max_new_tokens, **kw)
-    sync()
-    total_s = time.perf_counter() - t0
+    # the weights are quantised once, around all three calls: prefill_s does not carry it
+    with model.quantized_weights("fp8") if a.weight_dtype == "fp8" else contextlib.nullcontext():
+        model.generate(ids, amask, max_new_tokens=1, **kw)
+        sync()
+        t0 = time.perf_counter()
+        model.generate(ids, amask, max_new_tokens=1, **kw)
+        sync()
+        prefill_s = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        out = model.generate(ids, amask, max_new_tokens=a.max_new_tokens, **kw)
+        sync()
+        total_s = time.perf_counter() - t0
     new = out[:, T:].tolist()
     recs = []
     for p, cont in zip(prompts, new):
@@ -147,6 +156,8 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
               "decode_tokens_per_s": (steps * len(prompts) / decode_s) if decode_s > 0 and steps else 0.0}
     if a.kv_dtype != "bf16":  # the default run's line is unchanged
         timing["kv_dtype"] = a.kv_dtype
+    if a.weight_dtype != "bf16":
+        timing["weight_dtype"] = a.weight_dtype
     if a.sampler != "torch":
         timing["sampler"] = a.sampler
     print(json.dumps(timing), flush=True)

@@ -107,6 +107,10 @@ class LlamaForCausalLM:
             raise ValueError("fp8 needs bf16 compute on an MI355X")
         self.proj = Fp8Projections(self, fp8_wgrad) if fp8 else Bf16Projections(self)
         self.fp8 = self.proj.lin if fp8 else None  # the fp8 state (Fp8Linears) behind self.proj
+        # fp8 weight-only decode: inside ``quantized_weights`` {weight key (``_wkey``): (codes, exps)}, else None;
+        # ``_wq_ws``: the fp32 workspace the ``ops.gemv_w8`` launches share (they run one after the other)
+        self.wq = None
+        self._wq_ws = None
 
     # ------------------------------------------------------------------ init / io
     @torch.no_grad()
@@ -305,6 +309,72 @@ class LlamaForCausalLM:
         finally:
             self.training, self.proj = saved
 
+    @staticmethod
+    def _wkey(names) -> str:
+        return names if isinstance(names, str) else "|".join(names)
+
+    def _proj(self, x: torch.Tensor, names) -> torch.Tensor:
+        """One projection ``x @ W^T`` of the decode / extend step; ``names``: a parameter name, or the names of a fused
+        group.  Inside ``quantized_weights`` the fp8 kernel streams the codes where it can (``ops.gemv_w8_supported``);
+        everywhere else ``ops.mm_nt`` runs on the shadow, which then holds the same, rounded values."""
+        if self.wq is not None:
+            codes, exps = self.wq[self._wkey(names)]
+            if ops.gemv_w8_supported(x, codes):
+                return ops.gemv_w8(x, codes, exps, workspace=self._wq_ws)
+        return ops.mm_nt(x, self._w(names) if isinstance(names, str) else self._fused(names, "shadow"))
+
+    @contextlib.contextmanager
+    def quantized_weights(self, dtype: str = "fp8"):
+        """Inside the context the decoder's projection weights (per layer the fused q|k|v, o, the fused gate|up, down;
+        and the lm head) are the fp8 weight-only model: e4m3 codes plus one exponent per 128 input features
+        (``ops.gemv.quantize_weight``, the KV cache's format), kept on ``self.wq`` for ``ops.gemv_w8``, and the
+        dequantised values written over the compute-dtype shadow, so every other path -- whole-prompt prefill,
+        ``extend``, ``forward``, the uncached recompute, the CPU, ``--ops torch`` -- computes with the same rounded
+        weights.  The fp32 masters, the embedding gather and the norm weights are untouched; on exit the shadow is
+        the master's again.  Nesting is refused; so is a weight whose K is not a multiple of 128."""
+        from ..ops import gemv
+        if dtype != "fp8":
+            raise ValueError(f"quantized_weights: dtype must be 'fp8', not {dtype!r}")
+        if self.wq is not None:
+            raise RuntimeError("quantized_weights: the model is already inside the context (nesting is refused)")
+        targets = []
+        for i in range(self.config.num_hidden_layers):
+            p = f"model.layers.{i}."
+            targets += [self._qkv_names[i], p + "self_attn.o_proj.weight", self._gu_names[i],
+                        p + "mlp.down_proj.weight"]
+        targets.append(self._lm_name())
+        views = {self._wkey(t): self._w(t) if isinstance(t, str) else self._fused(t, "shadow") for t in targets}
+        for key, w in views.items():
+            if w.shape[1] % gemv.GROUP:
+                raise ValueError(f"fp8 weights need every projection's K to be a multiple of {gemv.GROUP}: {key} is "
+                                 f"{tuple(w.shape)}")
+        alias = self.store.separate_shadow is None  # fp32 compute: the shadow IS the master
+        if alias and self.config.tie_word_embeddings:
+            raise ValueError("quantized_weights: with fp32 compute and tied embeddings the lm head cannot be rounded "
+                             "without changing the embedding table")
+        saved = {k: w.clone() for k, w in views.items()} if alias else None
+        wq, need = {}, 0
+        hip = self.device.type == "cuda" and ops._ext.get_backend() != "torch"
+        with torch.no_grad():
+            for key, w in views.items():
+                codes, exps = gemv.quantize_weight(w)
+                w.copy_(gemv.dequantize_weight(codes, exps, w.dtype))
+                wq[key] = (codes, exps)
+                if hip:
+                    need = max(need, gemv.gemv_w8_workspace_numel(w.shape[0], w.shape[1]))
+        self.wq = wq
+        self._wq_ws = torch.empty(need, dtype=torch.float32, device=self.device) if need else None
+        try:
+            yield self
+        finally:
+            self.wq = self._wq_ws = None
+            with torch.no_grad():
+                if alias:
+                    for k, w in views.items():
+                        w.copy_(saved[k])
+                else:
+                    self.store.sync_shadow()
+
     def new_cache(self, batch: int, s_max: int, kv_dtype: str = "bf16"):
         """``kv_dtype`` "fp8": K and V rows as e4m3 codes plus a row exponent (``ops.decode``), about half the bytes."""
         return ops.KVCache(self.config, batch, s_max, self.device, self.compute_dtype, kv_dtype=kv_dtype)
@@ -352,18 +422,18 @@ class LlamaForCausalLM:
         L = c.num_hidden_layers
         for i in range(L):
             p = f"model.layers.{i}."
-            qkv = ops.mm_nt(y, self._fused(self._qkv_names[i], "shadow"))
+            qkv = self._proj(y, self._qkv_names[i])
             if c.qk_norm:  # in place on the new row; the decode kernel rotates what it finds there
                 ops.qk_norm(qkv, self._m(p + "self_attn.q_norm.weight"), self._m(p + "self_attn.k_norm.weight"),
                             c.num_attention_heads, c.num_key_value_heads, c.head_dim, eps)
             o = ops.attention_decode(qkv, cache, i, cos, sin)
-            a = ops.mm_nt(o, self._w(p + "self_attn.o_proj.weight"))
+            a = self._proj(o, p + "self_attn.o_proj.weight")
             y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"), None, eps, cdt)
-            gu = ops.mm_nt(y, self._fused(self._gu_names[i], "shadow"))
-            m = ops.mm_nt(ops.swiglu(gu), self._w(p + "mlp.down_proj.weight"))
+            gu = self._proj(y, self._gu_names[i])
+            m = self._proj(ops.swiglu(gu), p + "mlp.down_proj.weight")
             nxt = f"model.layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "model.norm.weight"
             y, h = ops.add_rmsnorm(h, m, self._m(nxt), None, eps, cdt)
-        logits = self._capped(ops.mm_nt(y, self._w(self._lm_name())).float())
+        logits = self._capped(self._proj(y, self._lm_name()).float())
         cache.pos += 1
         return logits
 
@@ -395,20 +465,20 @@ class LlamaForCausalLM:
             L = c.num_hidden_layers
             for i in range(L):
                 p = f"model.layers.{i}."
-                qkv = ops.mm_nt(y, self._fused(self._qkv_names[i], "shadow"))
+                qkv = self._proj(y, self._qkv_names[i])
                 if c.qk_norm:  # in place on the new rows; the extend kernel rotates what it finds there
                     ops.qk_norm(qkv, self._m(p + "self_attn.q_norm.weight"), self._m(p + "self_attn.k_norm.weight"),
                                 c.num_attention_heads, c.num_key_value_heads, c.head_dim, eps)
                 o = ops.attention_extend(qkv, cache, i, cos, sin, T)
-                a = ops.mm_nt(o, self._w(p + "self_attn.o_proj.weight"))
+                a = self._proj(o, p + "self_attn.o_proj.weight")
                 y, h = ops.add_rmsnorm(h, a, self._m(p + "post_attention_layernorm.weight"), None, eps, cdt)
-                gu = ops.mm_nt(y, self._fused(self._gu_names[i], "shadow"))
-                m = ops.mm_nt(ops.swiglu(gu), self._w(p + "mlp.down_proj.weight"))
+                gu = self._proj(y, self._gu_names[i])
+                m = self._proj(ops.swiglu(gu), p + "mlp.down_proj.weight")
                 nxt = f"model.layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "model.norm.weight"
                 y, h = ops.add_rmsnorm(h, m, self._m(nxt), None, eps, cdt)
             if last_only:
                 y = y.view(B, T, -1)[:, -1].contiguous()
-            logits = self._capped(ops.mm_nt(y, self._w(self._lm_name())).float())
+            logits = self._capped(self._proj(y, self._lm_name()).float())
         cache.advance(T)
         return logits if last_only else logits.view(B, T, -1)
 
@@ -416,7 +486,7 @@ class LlamaForCausalLM:
                  max_new_tokens: int = 32, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  eos_token_id=_CONFIG, pad_token_id=_CONFIG, seed: int = 0, use_cache: bool = True,
                  hip_graph="auto", return_logits: bool = False, prefill_chunk: int = 0,
-                 kv_dtype: str = "bf16", sampler: str = "torch"):
+                 kv_dtype: str = "bf16", sampler: str = "torch", weight_dtype: str = "bf16"):
         """Continue a (left-padded) prompt batch ``input_ids`` [B, T]; returns the token ids [B, T + n], n <=
         ``max_new_tokens`` (generation ends early once every row has produced ``eos_token_id``; a finished row is
         filled with ``pad_token_id``).  ``temperature`` 0 is greedy; otherwise ``filter_logits`` (top-k, top-p) and
@@ -427,8 +497,19 @@ class LlamaForCausalLM:
         ``use_cache``): the prompt is prefilled through ``extend`` in pieces of N tokens.  ``kv_dtype``: "bf16", or "fp8"
         for the 8-bit KV cache (``new_cache``; needs ``use_cache``).  ``sampler``: "torch" (``filter_logits`` +
         ``torch.multinomial``) or "fused" (``ops.sample`` on one ``torch.rand`` number per row from the same seeded
-        generator: one HIP launch on the GPU); greedy is argmax under either."""
+        generator: one HIP launch on the GPU); greedy is argmax under either.  ``weight_dtype``: "bf16", or "fp8" for
+        the weight-only 8-bit projections (``quantized_weights`` is held for the call unless the caller already holds
+        it; needs ``use_cache``)."""
         c = self.config
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', not {weight_dtype!r}")
+        if weight_dtype != "bf16" and not use_cache:
+            raise ValueError("weight_dtype needs use_cache=True")
+        if weight_dtype == "fp8" and self.wq is None:
+            with self.quantized_weights("fp8"):
+                return self.generate(input_ids, attention_mask, max_new_tokens, temperature, top_k, top_p,
+                                     eos_token_id, pad_token_id, seed, use_cache, hip_graph, return_logits,
+                                     prefill_chunk, kv_dtype, sampler, weight_dtype)
         if sampler not in ("torch", "fused"):
             raise ValueError(f"sampler must be 'torch' or 'fused', not {sampler!r}")
         if kv_dtype != "bf16" and not use_cache:

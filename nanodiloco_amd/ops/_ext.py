@@ -181,8 +181,12 @@ def _declare(L: ctypes.CDLL):
         "nd_kv8_fill": [P, P, P, P, P, I, I, I, I, I, I, L64, P],
         # fused sampler (csrc/sample.hip): logits, u, tok, thr, nkept, B, V, ld, temperature, top_k, top_p, stream
         "nd_sample_topk_topp": [P, P, P, P, P, I, I, L64, F, I, F, P],
+        # fp8 weight-only skinny-M projection (csrc/gemv_w8.hip): x, codes, exps, out, ws, M, N, K, ldx, stream
+        "nd_gemv_w8": [P, P, P, P, P, I, I, I, L64, P],
+        "nd_gemv_w8_max_m": [],
+        "nd_gemv_w8_splits": [I, I],
         # mlp
-        "nd_swiglu_fwd": [P, P, I, L64, I, P],
+        "nd_swiglu_fwd":[P, P, I, L64, I, P],
         "nd_swiglu_bwd": [P, P, P, I, L64, I, P],
         "nd_swiglu_fwd_q": [P, P, L64, I, P, P, P, I, I, P],
         "nd_swiglu_bwd_q": [P, P, P, L64, I, P, P, P, I, I, P],
