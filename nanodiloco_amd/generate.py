@@ -4,7 +4,7 @@
         [--llama-config-file F] [--max-new-tokens 32] [--temperature 0] [--top-k 0] [--top-p 1.0] [--seed 0]
         [--dtype auto] [--residual-dtype auto] [--device auto] [--hip-graph auto|on|off]
         [--tokenizer PATH] [--prefill-chunk 0] [--kv-dtype bf16|fp8] [--sampler torch|fused]
-        [--weight-dtype bf16|fp8]
+        [--weight-dtype bf16|fp8|fp4]
 
 Single process.  Only the model weights of a checkpoint written by ``utils.checkpoint.save_checkpoint`` are read
 (``model.safetensors``), the config comes from ``--llama-config-file`` or the checkpoint's ``config.json`` -- as
@@ -22,7 +22,10 @@ with the one-launch HIP sampler (``ops.sample``; docs/DESIGN.md "Fused sampler")
 ``torch.multinomial``; the timing line then echoes ``sampler``.  The two draw different tokens from one seed.  ``--weight-dtype fp8`` runs the decoder's projections and the
 lm head on e4m3 codes plus one exponent per 128 input features (``model.quantized_weights``; docs/DESIGN.md "fp8
 weight-only decode"): the decode step streams the codes through ``ops.gemv_w8``, every other path computes with the
-same rounded weights; the timing line then echoes ``weight_dtype``.
+same rounded weights; the timing line then echoes ``weight_dtype``.  ``--weight-dtype fp4`` does the same with e2m1
+codes, two to a byte, plus one exponent per 32 input features (``ops.gemv_w4``; docs/DESIGN.md "fp4 weight-only
+decode"): about a quarter of the bf16 bytes and a much coarser rounding (relative weight error about 0.12 against
+0.027 for fp8).
 """
 from __future__ import annotations
 
@@ -60,8 +63,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="KV cache storage: bf16, or fp8 (e4m3 codes + one exponent per row)")
     p.add_argument("--sampler", default="torch", choices=["torch", "fused"],
                    help="with --temperature > 0: torch (filter_logits + multinomial) or fused (ops.sample, one launch)")
-    p.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
-                   help="projection weights: bf16, or fp8 weight-only (e4m3 codes + one exponent per 128 inputs)")
+    p.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "fp4"],
+                   help="projection weights: bf16, fp8 weight-only (e4m3 codes + one exponent per 128 inputs) or fp4 "
+                        "weight-only (e2m1 codes + one exponent per 32 inputs; lossy)")
     return p
 
 
@@ -128,7 +132,7 @@ def main(argv: Optional[List[str]] = None) -> List[Dict[str, Any]]:
     # the prompt pass alone (one new token), then the whole run: their difference is the decode time; one untimed
     # pass first, so that neither carries the first launches (code objects, GEMM algorithm selection)
     # the weights are quantised once, around all three calls: prefill_s does not carry it
-    with model.quantized_weights("fp8") if a.weight_dtype == "fp8" else contextlib.nullcontext():
+    with model.quantized_weights(a.weight_dtype) if a.weight_dtype != "bf16" else contextlib.nullcontext():
         model.generate(ids, amask, max_new_tokens=1, **kw)
         sync()
         t0 = time.perf_counter()

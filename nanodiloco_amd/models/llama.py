@@ -107,9 +107,11 @@ class LlamaForCausalLM:
             raise ValueError("fp8 needs bf16 compute on an MI355X")
         self.proj = Fp8Projections(self, fp8_wgrad) if fp8 else Bf16Projections(self)
         self.fp8 = self.proj.lin if fp8 else None  # the fp8 state (Fp8Linears) behind self.proj
-        # fp8 weight-only decode: inside ``quantized_weights`` {weight key (``_wkey``): (codes, exps)}, else None;
-        # ``_wq_ws``: the fp32 workspace the ``ops.gemv_w8`` launches share (they run one after the other)
+        # weight-only decode: inside ``quantized_weights`` {weight key (``_wkey``): (codes, exps)}, else None;
+        # ``wq_dtype``: their format ("fp8" / "fp4"); ``_wq_ws``: the fp32 workspace the ``ops.gemv_w8`` /
+        # ``ops.gemv_w4`` launches share (they run one after the other)
         self.wq = None
+        self.wq_dtype = None
         self._wq_ws = None
 
     # ------------------------------------------------------------------ init / io
@@ -315,26 +317,36 @@ class LlamaForCausalLM:
 
     def _proj(self, x: torch.Tensor, names) -> torch.Tensor:
         """One projection ``x @ W^T`` of the decode / extend step; ``names``: a parameter name, or the names of a fused
-        group.  Inside ``quantized_weights`` the fp8 kernel streams the codes where it can (``ops.gemv_w8_supported``);
-        everywhere else ``ops.mm_nt`` runs on the shadow, which then holds the same, rounded values."""
+        group.  Inside ``quantized_weights`` the held format's kernel streams the codes where it can
+        (``ops.gemv_w8_supported`` / ``ops.gemv_w4_supported``); everywhere else ``ops.mm_nt`` runs on the shadow,
+        which then holds the same, rounded values."""
         if self.wq is not None:
             codes, exps = self.wq[self._wkey(names)]
-            if ops.gemv_w8_supported(x, codes):
+            if self.wq_dtype == "fp4":
+                if ops.gemv_w4_supported(x, codes):
+                    return ops.gemv_w4(x, codes, exps, workspace=self._wq_ws)
+            elif ops.gemv_w8_supported(x, codes):
                 return ops.gemv_w8(x, codes, exps, workspace=self._wq_ws)
         return ops.mm_nt(x, self._w(names) if isinstance(names, str) else self._fused(names, "shadow"))
 
     @contextlib.contextmanager
     def quantized_weights(self, dtype: str = "fp8"):
         """Inside the context the decoder's projection weights (per layer the fused q|k|v, o, the fused gate|up, down;
-        and the lm head) are the fp8 weight-only model: e4m3 codes plus one exponent per 128 input features
-        (``ops.gemv.quantize_weight``, the KV cache's format), kept on ``self.wq`` for ``ops.gemv_w8``, and the
+        and the lm head) are a weight-only model.  ``dtype`` "fp8": e4m3 codes plus one exponent per 128 input
+        features (``ops.gemv.quantize_weight``, the KV cache's format) for ``ops.gemv_w8``; "fp4": e2m1 codes, two to
+        a byte, plus one exponent per 32 input features (``ops.gemv.quantize_weight_fp4``) for ``ops.gemv_w4``.  The
+        codes are kept on ``self.wq`` (their format on ``self.wq_dtype``), and the
         dequantised values written over the compute-dtype shadow, so every other path -- whole-prompt prefill,
         ``extend``, ``forward``, the uncached recompute, the CPU, ``--ops torch`` -- computes with the same rounded
         weights.  The fp32 masters, the embedding gather and the norm weights are untouched; on exit the shadow is
-        the master's again.  Nesting is refused; so is a weight whose K is not a multiple of 128."""
+        the master's again.  Nesting is refused, whichever format is held; so is a weight whose K is not a multiple
+        of 128."""
         from ..ops import gemv
-        if dtype != "fp8":
-            raise ValueError(f"quantized_weights: dtype must be 'fp8', not {dtype!r}")
+        if dtype not in ("fp8", "fp4"):
+            raise ValueError(f"quantized_weights: dtype must be 'fp8' or 'fp4', not {dtype!r}")
+        quantize, dequantize, ws_numel = {
+            "fp8": (gemv.quantize_weight, gemv.dequantize_weight, gemv.gemv_w8_workspace_numel),
+            "fp4": (gemv.quantize_weight_fp4, gemv.dequantize_weight_fp4, gemv.gemv_w4_workspace_numel)}[dtype]
         if self.wq is not None:
             raise RuntimeError("quantized_weights: the model is already inside the context (nesting is refused)")
         targets = []
@@ -346,7 +358,7 @@ class LlamaForCausalLM:
         views = {self._wkey(t): self._w(t) if isinstance(t, str) else self._fused(t, "shadow") for t in targets}
         for key, w in views.items():
             if w.shape[1] % gemv.GROUP:
-                raise ValueError(f"fp8 weights need every projection's K to be a multiple of {gemv.GROUP}: {key} is "
+                raise ValueError(f"{dtype} weights need every projection's K to be a multiple of {gemv.GROUP}: {key} is "
                                  f"{tuple(w.shape)}")
         alias = self.store.separate_shadow is None  # fp32 compute: the shadow IS the master
         if alias and self.config.tie_word_embeddings:
@@ -357,17 +369,17 @@ class LlamaForCausalLM:
         hip = self.device.type == "cuda" and ops._ext.get_backend() != "torch"
         with torch.no_grad():
             for key, w in views.items():
-                codes, exps = gemv.quantize_weight(w)
-                w.copy_(gemv.dequantize_weight(codes, exps, w.dtype))
+                codes, exps = quantize(w)
+                w.copy_(dequantize(codes, exps, w.dtype))
                 wq[key] = (codes, exps)
                 if hip:
-                    need = max(need, gemv.gemv_w8_workspace_numel(w.shape[0], w.shape[1]))
-        self.wq = wq
+                    need = max(need, ws_numel(w.shape[0], w.shape[1]))
+        self.wq, self.wq_dtype = wq, dtype
         self._wq_ws = torch.empty(need, dtype=torch.float32, device=self.device) if need else None
         try:
             yield self
         finally:
-            self.wq = self._wq_ws = None
+            self.wq = self.wq_dtype = self._wq_ws = None
             with torch.no_grad():
                 if alias:
                     for k, w in views.items():
@@ -497,16 +509,18 @@ class LlamaForCausalLM:
         ``use_cache``): the prompt is prefilled through ``extend`` in pieces of N tokens.  ``kv_dtype``: "bf16", or "fp8"
         for the 8-bit KV cache (``new_cache``; needs ``use_cache``).  ``sampler``: "torch" (``filter_logits`` +
         ``torch.multinomial``) or "fused" (``ops.sample`` on one ``torch.rand`` number per row from the same seeded
-        generator: one HIP launch on the GPU); greedy is argmax under either.  ``weight_dtype``: "bf16", or "fp8" for
-        the weight-only 8-bit projections (``quantized_weights`` is held for the call unless the caller already holds
-        it; needs ``use_cache``)."""
+        generator: one HIP launch on the GPU); greedy is argmax under either.  ``weight_dtype``: "bf16", or "fp8" /
+        "fp4" for the weight-only 8-bit / 4-bit projections (``quantized_weights`` is held for the call unless the
+        caller already holds it, in the same format: another one is refused; needs ``use_cache``)."""
         c = self.config
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', not {weight_dtype!r}")
+        if weight_dtype not in ("bf16", "fp8", "fp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'fp4', not {weight_dtype!r}")
         if weight_dtype != "bf16" and not use_cache:
             raise ValueError("weight_dtype needs use_cache=True")
-        if weight_dtype == "fp8" and self.wq is None:
-            with self.quantized_weights("fp8"):
+        if weight_dtype != "bf16" and self.wq is not None and self.wq_dtype != weight_dtype:
+            raise ValueError(f"weight_dtype {weight_dtype!r} asked for inside quantized_weights({self.wq_dtype!r})")
+        if weight_dtype != "bf16" and self.wq is None:
+            with self.quantized_weights(weight_dtype):
                 return self.generate(input_ids, attention_mask, max_new_tokens, temperature, top_k, top_p,
                                      eos_token_id, pad_token_id, seed, use_cache, hip_graph, return_logits,
                                      prefill_chunk, kv_dtype, sampler, weight_dtype)

@@ -14,7 +14,8 @@ from .attention import attention, rope_cache, set_attn_fused_stats, key_start, c
 from .decode import KVCache, attention_decode, cache_fill, decode_split, attention_extend, attention_extend_torch, \
     attn_extend_launch, extend_workspace, extend_qblock
 from .sample import sample
-from .gemv import gemv_w8, gemv_w8_supported, gemv_w8_workspace
+from .gemv import gemv_w8, gemv_w8_supported, gemv_w8_workspace, gemv_w4, gemv_w4_supported, gemv_w4_workspace, \
+    gemv_w4_workspace_numel
 from .cross_entropy import lm_head_ce, lm_head_ce_parts, lm_head_loss, logit_softcap, LMHeadLoss, IGNORE_INDEX
 from .optim import adamw_step, global_grad_norm, pseudograd, outer_nesterov, frag_pseudograd, frag_outer_mix, \
     SpanTable
@@ -33,6 +34,7 @@ __all__ = ["hip_available", "set_backend", "get_backend", "ExtensionMissing", "l
            "rmsnorm", "rmsnorm_res", "add_rmsnorm", "qk_norm", "qk_norm_rope", "set_attn_fused_stats", "embedding", "swiglu", "attention", "rope_cache", "doc_bounds", "check_doc_bounds",
            "KVCache", "attention_decode", "cache_fill", "decode_split", "attention_extend", "attention_extend_torch",
            "attn_extend_launch", "extend_workspace", "extend_qblock", "sample", "gemv_w8", "gemv_w8_supported", "gemv_w8_workspace",
+           "gemv_w4", "gemv_w4_supported", "gemv_w4_workspace", "gemv_w4_workspace_numel",
            "lm_head_ce", "lm_head_ce_parts", "LMHeadLoss", "lm_head_loss", "logit_softcap",
            "IGNORE_INDEX", "adamw_step", "global_grad_norm", "pseudograd", "outer_nesterov", "pseudograd_q", "qreduce",
            "outer_nesterov_q", "pseudograd_q_ef", "qreduce_ef", "pseudograd_topk", "outer_nesterov_topk",

@@ -185,6 +185,9 @@ def _declare(L: ctypes.CDLL):
         "nd_gemv_w8": [P, P, P, P, P, I, I, I, L64, P],
         "nd_gemv_w8_max_m": [],
         "nd_gemv_w8_splits": [I, I],
+        # fp4 weight-only skinny-M projection (csrc/gemv_w4.hip): the same arguments, codes [N, K / 2], exps [N, K / 32]
+        "nd_gemv_w4": [P, P, P, P, P, I, I, I, L64, P],
+        "nd_gemv_w4_splits": [I, I],
         # mlp
         "nd_swiglu_fwd":[P, P, I, L64, I, P],
         "nd_swiglu_bwd": [P, P, P, I, L64, I, P],
